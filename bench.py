@@ -11,7 +11,11 @@ update + latent hand-off, all inputs resident in HBM); the K timed steps cycle t
 [inversion, inversion, inversion, composition], so ``value`` = the job's average steps/s.  Synthetic latents /
 conditioning / seeded weights of the exact architecture (no checkpoint or dataset is reachable).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds the legs that take runs of their
+own: the sequential-inversion form of the same K steps, per-step-kind timings, the roofline leg (eager repeat with per-launch
+HIP events) and the CPU baseline.  --dump-outputs DIR writes the latents the timed steps leave behind as float32 .npy files.
 
 N > 1: one rank per GPU.  Launched by torch.distributed.run (RANK / WORLD_SIZE set) this process is one rank; launched plainly it
 starts the N ranks itself as child processes (`python -m torch.distributed.run ... bench.py <same flags>`, BEFORE anything here
@@ -54,8 +58,15 @@ def parse():
                                                              "reference's own demo size 1280x720 is --latent-h 90 --latent-w 160)")
     ap.add_argument("--latent-w", type=int, default=0)
     ap.add_argument("--no-graphs", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the metric's K steps also run the legs that take runs of their own: sequential-inversion form of "
+                         "the same steps, per-step-kind timings, roofline leg, CPU baseline (each can be dropped with --no-*)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave out the roofline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed -- the latents of every stream (inversion clip(s), "
+                         "composition) as left by its most recent step, the last timed step's output among them -- as "
+                         "DIR/<name>.npy, float32, at most 64 MB in all (a fixed, seeded sample of a larger array)")
     ap.add_argument("--mix", default="job", choices=["job", "inv", "comp"],
                     help="diagnostics: time only inversion (B=1) or only composition (B=5) steps; the metric is --mix job")
     ap.add_argument("--workload", default="boat_surf", choices=["boat_surf", "longclip", "demo"],
@@ -65,7 +76,7 @@ def parse():
                          "(3 x inverse.py + composite.py, VAE / CLIP / file IO included; tools/demo_job.py)")
     ap.add_argument("--sequential-inversions", action="store_true",
                     help="the job's three source inversions one step after the other on one stream (the definition of rounds 1-3; "
-                         "the default runs the three clips' batch-1 steps concurrently on three streams and reports this form beside it)")
+                         "the default runs the three clips' batch-1 steps concurrently on three streams; --full reports this form beside it)")
     ap.add_argument("--batch-inversions", action="store_true",
                     help="diagnostic: the 3 source inversions of the job share one UNet call per step (batch 3, "
                          "I2VGenXLPipeline.invert_many) instead of three calls at batch 1; --steps must be a multiple of 4")
@@ -269,6 +280,37 @@ class Job:
             self.inversion_step()
         elif k % 4 == 0:  # steps k, k+1, k+2 of the mix are the three sources' inversion steps: one batched call
             self.batched_inversion_step()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(arrays, out_dir):
+    """--dump-outputs: {name: device tensor} -> out_dir/<name>.npy in float32.  An array beyond its share of the 64 MB limit is
+    replaced by a fixed, seeded sample of its flattened elements (same indices on every run of the same shape)."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1) // 4
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
+def job_outputs(job):
+    """what a caller of each stream of the timed path holds after the timed steps: the latents its most recent step left"""
+    out = {}
+    if job.concurrent:
+        for j, st in enumerate(job.inv_states):
+            out[f"inversion_latents_clip{j}"] = st["latents"]
+    elif job.batch_inversions:
+        out["inversion_latents_batch3"] = job.inv3_state["latents"]
+    else:
+        out["inversion_latents"] = job.inv_state["latents"]
+    out["composition_latents"] = job.comp_state["latents"]
+    return out
 
 
 def roofline_leg(job, steps):
@@ -530,6 +572,8 @@ def longclip(args, rank, world, device, dist):
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs({"inversion_latents": st["latents"]}, args.dump_outputs)
     if dist is not None:
         tt = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -674,6 +718,8 @@ def main():
     if args.workload == "longclip":
         return longclip(args, rank, world, device, dist)
     if args.workload == "demo":
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs covers --workload boat_surf / longclip (the demo writes its own result files)")
         return demo(args)
     if args.pmc_pass:
         args.no_graphs = args.no_roofline = args.no_cpu_baseline = True
@@ -736,13 +782,16 @@ def main():
 
     own = [0.0]
     dt = timed_region()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(job_outputs(job), args.dump_outputs)
     ident["ms_per_step"] = round(own[0] / args.steps * 1e3, 3)  # this rank's own clock around the same K steps (the line's is the MAX)
     idents = [ident]
     if dist is not None:
         idents = [None] * world
         dist.all_gather_object(idents, ident)
+    # --full only from here to the result line: runs of their own beside the metric's K steps
     dt_seq = None
-    if concurrent:  # the same K steps in the rounds 1-3 form (one inversion step after the other), reported beside the metric
+    if args.full and concurrent:  # the same K steps in the rounds 1-3 form (one inversion step after the other), reported beside the metric
         job.concurrent = False
         dt_seq = timed_region()
         job.concurrent = True
@@ -757,19 +806,23 @@ def main():
         return (time.perf_counter() - a) / n * 1e3
 
     was_concurrent, job.concurrent = job.concurrent, False
-    inv_ms = timed(job.inversion_step, 3)
-    inv_conc_ms = None
-    if was_concurrent:
-        def period():
-            for j in range(3):
-                job.concurrent_inversion_step(j)
-            job.join_inversions()
-        job.inv_i = 0
-        inv_conc_ms = timed(period, 3) / 3
-    job.comp_i = 0
-    comp_ms = timed(job.composition_step, 2)       # Q/K-injection-only steps: 45 of the job's 50
-    job.comp_i = 19
-    compf_ms = timed(lambda: (setattr(job, "comp_i", 19), job.composition_step()), 2)  # feature-injection step: 5 of 50
+    inv_ms = inv_conc_ms = comp_ms = compf_ms = None
+    if args.full:
+        inv_ms = timed(job.inversion_step, 3)
+        if was_concurrent:
+            def period():
+                for j in range(3):
+                    job.concurrent_inversion_step(j)
+                job.join_inversions()
+            job.inv_i = 0
+            inv_conc_ms = timed(period, 3) / 3
+        job.comp_i = 0
+        comp_ms = timed(job.composition_step, 2)       # Q/K-injection-only steps: 45 of the job's 50
+        job.comp_i = 19
+        compf_ms = timed(lambda: (setattr(job, "comp_i", 19), job.composition_step()), 2)  # feature-injection step: 5 of 50
+
+    def r3(v):
+        return None if v is None else round(v, 3)
 
     out = None
     if rank == 0:
@@ -808,16 +861,17 @@ def main():
                 "hip_graphs": not args.no_graphs,
                 "loop_invariant_conditioning": "context tokens, cross-attention K/V of them and the image-latent stem are computed once "
                                                "per loop (I2VGenXLUNet.prepare_conditioning), bit-identical to recomputing them per step",
-                "inversion_step_ms": round(inv_ms, 3),
-                "inversion_step_ms_three_clips_concurrent": None if inv_conc_ms is None else round(inv_conc_ms, 3),
+                "inversion_step_ms": r3(inv_ms),  # (this and the other per-kind / sequential figures: --full, else null)
+                "inversion_step_ms_three_clips_concurrent": r3(inv_conc_ms),
                 "sequential_inversions": None if dt_seq is None else {
                     "value": round(world * args.steps / dt_seq, 4), "ms_per_step": round(dt_seq / args.steps * 1e3, 3),
                     "note": "the same K steps with the three inversion steps of a period one after the other on one stream (rounds 1-3)"},
-                "composition_step_ms": round(comp_ms, 3),
-                "composition_feature_injection_step_ms": round(compf_ms, 3),
+                "composition_step_ms": r3(comp_ms),
+                "composition_feature_injection_step_ms": r3(compf_ms),
                 "timed_composition_steps": {"qk_injection_only": sum(1 for j in range(sum(1 for k in range(args.steps) if job.is_comp(k))) if j % 10 != 9),
                                             "feature_injection": sum(1 for j in range(sum(1 for k in range(args.steps) if job.is_comp(k))) if j % 10 == 9)},
-                "job_average_ms_per_step": round((150 * (inv_conc_ms if inv_conc_ms is not None else inv_ms) + 45 * comp_ms + 5 * compf_ms) / 200, 3),
+                "job_average_ms_per_step": None if inv_ms is None else
+                round((150 * (inv_conc_ms if inv_conc_ms is not None else inv_ms) + 45 * comp_ms + 5 * compf_ms) / 200, 3),
                 "work_not_executed": "every step delivers the reference loop's result; what the engine does not run, because nothing reads it "
                                      "or it is computed twice (each switchable, each with a parity test): (1) composition, conv_out-"
                                      "injection steps (5 of 50): the two destination chunks (unet.prune_dead_chunks, round 2); (2) "
@@ -836,7 +890,7 @@ def main():
             },
         }
     # the two extra legs must never cost the metric line: a failure is reported in place of the object
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         try:
             job.concurrent = False  # (per-launch HIP-event brackets: one stream, one launch at a time)
             out["roofline"] = roofline_leg(job, args.steps)
@@ -844,7 +898,7 @@ def main():
             out["config"]["executed_tflops"] = round(out["roofline"]["executed_matrix_tflop_all_steps"] / dt, 2)
         except Exception as e:  # noqa: BLE001
             out["roofline"] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(args.frames, args.latent)
         except Exception as e:  # noqa: BLE001

@@ -267,22 +267,36 @@ def test_g8_reference_conditioning_layout(golden_dir):
 
 
 def test_committed_fixtures_are_what_the_reference_produces(tmp_path):
-    """Build container only (skipped wherever /root/reference is absent, e.g. on the GPU box): tools/gen_golden.py -- which IMPORTS the
-    reference's own pnp_utils.py / pipeline_i2vgen_xl.py / utils.py -- regenerates every fixture under tests/golden/ into a scratch
-    directory, and each file must come out byte for byte as committed: the golden vectors are outputs of the reference's code, not of
-    the oracle's, and nobody edited them."""
+    """tools/gen_golden.py -- which IMPORTS the reference's own pnp_utils.py / pipeline_i2vgen_xl.py / utils.py -- wrote every
+    fixture under tests/golden/ and, beside them, SHA256SUMS: the digest of each file as the reference's code produced it.  Every
+    committed fixture must match its digest byte for byte (the golden vectors are outputs of the reference's code, not of the
+    oracle's, and nobody edited them).  Where a reference checkout sits at the place gen_golden.py reads it from, the fixtures are
+    also regenerated into a scratch directory and must come out byte for byte as committed."""
+    import hashlib
+    import importlib.util
     import subprocess
     import sys
-    if not os.path.isdir("/root/reference/i2vgen-xl"):
-        pytest.skip("the reference checkout is not present here")
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    gold = os.path.join(repo, "tests", "golden")
+    sums = {}
+    for line in open(os.path.join(gold, "SHA256SUMS")):
+        digest, name = line.split()
+        sums[name] = digest
+    committed = sorted(f for f in os.listdir(gold) if f.endswith((".npz", ".json")))
+    assert committed == sorted(sums), (committed, sorted(sums))
+    for f in committed:
+        assert hashlib.sha256(open(os.path.join(gold, f), "rb").read()).hexdigest() == sums[f], f"{f} differs from its recorded digest"
+    spec = importlib.util.spec_from_file_location("gen_golden", os.path.join(repo, "tools", "gen_golden.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    if not os.path.isdir(os.path.join(gen.REF, "i2vgen-xl")):
+        return  # no reference checkout here: the digests above are the check
     env = dict(os.environ, MVOC_GOLDEN_OUT=str(tmp_path))
     r = subprocess.run([sys.executable, os.path.join(repo, "tools", "gen_golden.py")], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     made = sorted(f for f in os.listdir(tmp_path) if f.endswith((".npz", ".json")))
     assert made, "gen_golden.py wrote nothing"
-    gold = os.path.join(repo, "tests", "golden")
-    committed = sorted(f for f in os.listdir(gold) if f.endswith((".npz", ".json")))
     assert made == committed, (made, committed)
+    assert open(os.path.join(tmp_path, "SHA256SUMS")).read() == open(os.path.join(gold, "SHA256SUMS")).read()
     for f in made:
         assert open(os.path.join(tmp_path, f), "rb").read() == open(os.path.join(gold, f), "rb").read(), f"{f} differs from the committed fixture"

@@ -8,10 +8,10 @@ OUT=${1:-gpurun_out/ev}; TAG=${2:-ev}
 mkdir -p $OUT
 timeout 3000 python -m pytest tests -q -m gpu > $OUT/gpu_tests.log 2>&1; tail -3 $OUT/gpu_tests.log
 for i in 1 2; do
-  python bench.py > $OUT/bench_run$i.json 2> /dev/null
+  python bench.py --full > $OUT/bench_run$i.json 2> /dev/null
   [ -d tools/lab/r5_tree ] && (cd tools/lab/r5_tree && python bench.py --no-cpu-baseline 2>/dev/null) > $OUT/bench_round5_tree_same_box_run$i.json
 done
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_steps20.json 2> /dev/null
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_steps20.json 2> /dev/null
 bash tools/lab/ab_bench.sh > $OUT/switches_ab.txt 2>&1
 bash tools/prof_mix.sh $TAG 8 job > /dev/null 2>&1; cp gpurun_out/profmix_$TAG/summary.txt $OUT/mix_kernel_stats_summary.txt; cp gpurun_out/profmix_$TAG/kernel_stats.csv $OUT/mix_kernel_stats.csv
 bash tools/prof_mix.sh ${TAG}i 4 inv > /dev/null 2>&1; cp gpurun_out/profmix_${TAG}i/summary.txt $OUT/inversion_only_kernel_stats_summary.txt
@@ -29,7 +29,7 @@ python tools/tfused_bench.py > $OUT/tfused_bench.txt 2>&1
 python tools/gemm_bench.py 1 0 > $OUT/gemm_per_shape_B1.txt 2>&1
 python tools/gemm_bench.py 5 0 > $OUT/gemm_per_shape_B5.txt 2>&1
 python tools/attn_bench.py 5 > $OUT/attn_bench_B5.txt 2>&1
-python bench.py --latent-h 90 --latent-w 160 --no-cpu-baseline > $OUT/bench_latent_90x160.json 2> /dev/null
+python bench.py --full --latent-h 90 --latent-w 160 --no-cpu-baseline > $OUT/bench_latent_90x160.json 2> /dev/null
 python bench.py --workload demo > $OUT/demo_job_end_to_end.json 2> $OUT/demo.err
 head -12 $OUT/mix_kernel_stats_summary.txt
 python - $OUT <<'PY'

@@ -524,6 +524,14 @@ def gen_init_pnp():
     json.dump(out, open(os.path.join(OUT, "g10_init_pnp.json"), "w"), indent=0, sort_keys=True)
 
 
+def write_digests():
+    """SHA256SUMS beside the fixtures (sha256sum format): lets the CPU suite check the committed files without the reference"""
+    import hashlib
+    with open(os.path.join(OUT, "SHA256SUMS"), "w") as fh:
+        for f in sorted(x for x in os.listdir(OUT) if x.endswith((".npz", ".json"))):
+            fh.write(f"{hashlib.sha256(open(os.path.join(OUT, f), 'rb').read()).hexdigest()}  {f}\n")
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     if "--only-mask-pngs" in sys.argv:
@@ -542,6 +550,7 @@ def main():
     copy_mask_pngs()
     gen_loops(pnp_utils, pipeline_i2vgen_xl)
     gen_init_pnp()
+    write_digests()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
 
