@@ -14,6 +14,8 @@ import torch  # noqa: F401  (side effect: loads torch/lib/libamdhip64.so)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MVOC_HIP_LIB") or os.path.join(_HERE, "libmvoc_hip.so")  # override: A/B builds
 
+ABI_VERSION = 100  # MVOC_VERSION of include/mvoc_hip.h that the descriptors below mirror
+
 A_PLAIN, A_CONV3X3, A_TEMPORAL3 = 0, 1, 2
 ACT_NONE, ACT_GEGLU, ACT_SILU, ACT_GELU = 0, 1, 2, 3
 FAMILIES = ("gemm", "flash_attn", "temporal_attn", "groupnorm", "layernorm", "pnp", "misc", "temporal_fused")
@@ -135,6 +137,10 @@ def _load():
         fn = getattr(lib, name)  # AttributeError if the .so does not export what the header declares
         fn.restype = res
         fn.argtypes = args
+    if lib.mvoc_version() != ABI_VERSION:
+        # the ctypes descriptors are laid out for ABI_VERSION: another library would read them with other offsets
+        raise ImportError(f"{LIB_PATH} has mvoc_version() {lib.mvoc_version()}, these bindings need {ABI_VERSION}: rebuild it "
+                          "with `python -m mvoc_amd.build`")
     return lib
 
 

@@ -451,6 +451,8 @@ __device__ const uint4 g_zero16 = {0u, 0u, 0u, 0u};
 // PLAIN = 1: single-source plain linear (no taps, no second source, no upsampling) -- the per-K-step address work is one
 // pointer bump per LDS-DMA instead of the general gather bookkeeping (the K <= 1280 projections were VALU-issue bound:
 // ~22 non-MFMA instructions per MFMA in the general loop)
+// PLAIN = 2: the same with a second source, [a | a2] along K (the folded ff2 + proj_out of a transformer block reads
+// [f1 | h]: mvoc_amd.unet._TransformerBase): the pointers are rebuilt once, at the K step that crosses c1
 template <int WN, int WM, int TN, int TM, int NST, int PF = 0, int BKK = 64, int PLAIN = 0, int EPI = 0>
 __global__ __launch_bounds__(WN* WM * 64) void gemm_glds_kernel(const GemmArgs p) {
   static_assert(BKK == 64 || BKK == 32, "K step of 64 (128-byte staged rows) or 32 (64-byte rows)");
@@ -544,6 +546,12 @@ __global__ __launch_bounds__(WN* WM * 64) void gemm_glds_kernel(const GemmArgs p
   const half_t* aptr[PA];  // PLAIN: the lane's source pointer per staged row, bumped by one K step per issue
 #pragma unroll
   for (int i = 0; i < PA; ++i) aptr[i] = (vmask[i] & 1u) ? p.a + (size_t)rowoff[i] * p.lda + cch[i] + kbeg : zsrc;
+  if constexpr (PLAIN == 2) {
+    if (kbeg >= p.c1) {  // (split-K: a slice that starts in the second source)
+#pragma unroll
+      for (int i = 0; i < PA; ++i) aptr[i] = (vmask[i] & 1u) ? p.a2 + (size_t)rowoff[i] * p.lda2 + cch[i] + (kbeg - p.c1) : zsrc;
+    }
+  }
   int astep[PA];
 #pragma unroll
   for (int i = 0; i < PA; ++i) astep[i] = 0;
@@ -570,6 +578,13 @@ __global__ __launch_bounds__(WN* WM * 64) void gemm_glds_kernel(const GemmArgs p
                                          (__attribute__((address_space(3))) void*)(base + BN * ROW + (wave + i * NW) * 1024),
                                          16, 0, 0);
         aptr[i] += (vmask[i] & 1u) ? BKK : 0;
+      }
+      if constexpr (PLAIN == 2) {
+        ch0 += BKK;
+        if (ch0 == p.c1) {  // wave-uniform: the next K step reads the second source
+#pragma unroll
+          for (int i = 0; i < PA; ++i) aptr[i] = (vmask[i] & 1u) ? p.a2 + (size_t)rowoff[i] * p.lda2 + cch[i] : zsrc;
+        }
       }
       return;
     }
@@ -1136,6 +1151,16 @@ extern "C" int mvoc_gemm_f16(const mvoc_gemm_desc* d, void* stream) {
         return mvoc_check_launch("splitk_reduce_kernel");
       }
       return rc;
+    }
+  }
+  if (glds_ok && d->a_mode == MVOC_A_PLAIN && d->a2 != nullptr && !d->ln_rowsum) {
+    switch (tile) {  // ... and in their two-source form (PLAIN = 2)
+      case 11: return launch_glds<2, 2, 2, 2, 2, 0, 64, 2>(a, s);
+      case 12: if (d->act != MVOC_ACT_GEGLU) return launch_glds<1, 4, 5, 1, 2, 0, 64, 2>(a, s); break;
+      case 13: return launch_glds<1, 4, 2, 1, 2, 0, 64, 2>(a, s);
+      case 61: return launch_glds<2, 2, 2, 2, 2, 0, 32, 2>(a, s);
+      case 62: if (d->act != MVOC_ACT_GEGLU) return launch_glds<1, 4, 5, 1, 2, 0, 32, 2>(a, s); break;
+      default: break;
     }
   }
   if (glds_ok && d->a_mode == MVOC_A_PLAIN && d->a2 == nullptr && !d->upsample) {

@@ -92,6 +92,15 @@ def pack_geglu(w, b):
     return w[src].contiguous(), b[src].contiguous()
 
 
+def fold_proj_out(w2, b2, wp, bp):
+    """proj_out(ff2(f) + h) = Wp (W2 f + b2 + h) + bp = [Wp W2 | Wp] [f | h] + (Wp b2 + bp): the weights [C, 4C + C] and bias [C]
+    of the folded launch, formed in fp32 and rounded to fp16 once (Transformer2DModel / TransformerTemporalModel.ff_tail)"""
+    wp32 = wp.float()
+    w = torch.cat([wp32 @ w2.float(), wp32], dim=1)
+    b = wp32 @ b2.float() + bp.float()
+    return w.to(H16).contiguous(), b.to(H16).contiguous()
+
+
 def pack_xs_weights(w, consts=None):
     """[N, K] (N % 32 == 0, K % 16 == 0) + per-channel constants [N] -> the stream mvoc_xs_linear_f16 reads:
     [tile][K/16 + 1 pieces][lane 64][8]; piece s < K/16 in MFMA fragment order (element = W[32 tile + (lane & 31)][16 s +
@@ -281,6 +290,21 @@ class _TransformerBase:
         inner = self.proj_in.n
         self.transformer_blocks = [BasicTransformerBlock(sd, prefix + ".transformer_blocks.0", inner, heads, cross)]
         self.heads = heads
+        self.ff_out = None
+        if _TransformerBase.USE_PROJ_OUT_FOLD:
+            self.ff_out = Linear(*fold_proj_out(g(".transformer_blocks.0.ff.net.2.weight"), g(".transformer_blocks.0.ff.net.2.bias"),
+                                                g(".proj_out.weight"), g(".proj_out.bias")))
+
+    USE_PROJ_OUT_FOLD = os.environ.get("MVOC_PROJ_OUT_FOLD", "1") != "0"  # MVOC_PROJ_OUT_FOLD=0: A/B against ff2 + proj_out
+
+    def ff_tail(self, blk, f1, h, x):
+        """proj_out(ff2(f1) + h) + x, the block's last two linears.  Folded: ONE GEMM over the concat [f1 | h] with the weights
+        [Wp W2 | Wp] and the bias Wp b2 + bp (fold_proj_out) -- the ff2 output never exists, and the launch, epilogue and HBM round
+        trip of proj_out go away; the matrix work is the same (K = 4C + C instead of 4C, then C)."""
+        if self.ff_out is not None:
+            return self.ff_out(f1, x2=h, resid=x, sums=True)  # (the next module opens with a GroupNorm of this tensor)
+        h = blk.ff2(f1, resid=h)
+        return self.proj_out(h, resid=x, sums=True)
 
 
 class Transformer2DModel(_TransformerBase):
@@ -335,8 +359,7 @@ class Transformer2DModel(_TransformerBase):
                            kv_bdiv=ctx.frames_per_ctx)
         h = blk.attn2.to_out(a, resid=h, rowmom=True)
         f1 = blk.ff1.call_ln(h, blk.norm3, act=ACT_GEGLU)
-        h = blk.ff2(f1, resid=h)
-        return self.proj_out(h, resid=x, sums=True)  # (the next module opens with a GroupNorm of this tensor)
+        return self.ff_tail(blk, f1, h, x)
 
 
 class TransformerTemporalModel(_TransformerBase):
@@ -387,8 +410,7 @@ class TransformerTemporalModel(_TransformerBase):
             a = ops.temporal_attn(q, k, v, nsample=B, frames=F, hw=hw, heads=self.heads)
             h = attn.to_out(a, resid=h, rowmom=True)
         f1 = blk.ff1.call_ln(h, blk.norm3, act=ACT_GEGLU)
-        h = blk.ff2(f1, resid=h)
-        return self.proj_out(h, resid=x, sums=True)  # (the next module opens with a GroupNorm of this tensor)
+        return self.ff_tail(blk, f1, h, x)
 
 
 class ResnetBlock2D(Hookable):
