@@ -4,6 +4,9 @@ keys, hook registration order and output naming as the reference's ``i2vgen-xl/c
 
     PYTHONPATH=.. python composite.py --template_config configs/group_composite/template.yaml \
                                       --configs_json configs/group_composite/group_config.json [--synthetic] [--shard i/n]
+                                      [--dedup_sources]
+
+``--dedup_sources``: roles (background, objects) that are the same source share one UNet chunk.
 """
 import argparse
 import json
@@ -58,9 +61,11 @@ def output_suffix(config):
             + f"{config.fusion_step[0]}-{config.fusion_step[1]}")
 
 
-def main(template_config, configs_list, device, synthetic=False):
+def main(template_config, configs_list, device, synthetic=False, dedup_sources=False):
     from inverse import build_pipeline
     pipe = build_pipeline(device, synthetic)
+    if dedup_sources:
+        pipe.dedup_sources = True
     ddim_scheduler = DDIMScheduler.from_pretrained(PRETRAINED_MODEL_PATH, subfolder="scheduler")
     for entry in configs_list:
         if not entry["active"]:
@@ -119,6 +124,7 @@ if __name__ == "__main__":
     ap.add_argument("--configs_json", type=str, default="configs/group_composite/group_config.json")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--shard", type=str, default=None)
+    ap.add_argument("--dedup_sources", action="store_true", help="share one UNet chunk between roles that are the same source")
     args = ap.parse_args()
     template_config = OmegaConf.load(args.template_config)
     logging.basicConfig(level=logging.DEBUG if template_config.debug else logging.INFO,
@@ -129,4 +135,4 @@ if __name__ == "__main__":
     device = pick_device(template_config.device, args.shard)
     torch.set_grad_enabled(False)
     seed_everything(template_config.seed)
-    main(template_config, my_entries(configs_list, args.shard), device, args.synthetic)
+    main(template_config, my_entries(configs_list, args.shard), device, args.synthetic, args.dedup_sources)

@@ -297,6 +297,15 @@ typedef struct mvoc_pnp_desc {
 } mvoc_pnp_desc;
 int mvoc_pnp_blend_scatter_tokens(const mvoc_pnp_desc* d, void* stream);
 int mvoc_pnp_blend_scatter_nchw(const mvoc_pnp_desc* d, void* stream);
+/* Source de-duplication (pipeline.py dedup_sources): roles that are the same source share one chunk, the batch is
+ * [s_0..s_{nsrc-1}, uncond, cond] (or [s_0..s_{nsrc-1}, cond] with ndst = 1).  Chunk 0 is the background's, object j reads
+ * chunk obj_chunk[j] (a HOST array of d->nobj entries, read during the call only: the map travels in the kernel arguments,
+ * so a captured graph replays it), the destination chunks start at nsrc and the base is chunk 0, or the last chunk when
+ * base_chunk0 == 0.  Same arithmetic and object order as above: the destination rows are bit-identical to the unmapped
+ * entry on the sources expanded back to nobj + 1 chunks.  Requires 1 <= nsrc <= nobj + 1 and 0 <= obj_chunk[j] < nsrc
+ * (else -1 and an error text). */
+int mvoc_pnp_blend_scatter_tokens_mapped(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, void* stream);
+int mvoc_pnp_blend_scatter_nchw_mapped(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Loop glue on [B,4,F,h,w] fp16 latents, BIT-EXACT vs the reference's eager fp16 op chain.

@@ -18,7 +18,23 @@ struct PnpArgs {
   int ndst;      // trailing destination chunks: 2 = [uncond, cond] (the reference's CFG layout), 1 = [cond] (CFG off)
   float sy, sx;  // nearest-resize scales mask_h/height, mask_w/width (as F.interpolate computes them)
   long total;    // work items per tensor
+  // (MAPPED kernels) source de-duplication: chunks 0..nsrc-1 are sources, object j reads chunk (obj_map >> 4j) & 15.  A packed
+  // scalar, not an array: the run-time object loop indexes it with a shift (a run-time-indexed array member risks scratch)
+  int nsrc;
+  unsigned obj_map;
 };
+
+template <bool MAPPED>
+__device__ __forceinline__ int obj_chunk(const PnpArgs& p, int j) {
+  if constexpr (MAPPED) return (int)((p.obj_map >> (4 * j)) & 15u);
+  return j + 1;
+}
+
+template <bool MAPPED>
+__device__ __forceinline__ int chunk_count(const PnpArgs& p) {
+  if constexpr (MAPPED) return p.nsrc + p.ndst;
+  return p.nobj + 1 + p.ndst;
+}
 
 __device__ __forceinline__ float blend16(float inj, float obj, float m) {
   const float om = r16(1.0f - m);
@@ -30,6 +46,7 @@ __device__ __forceinline__ int nearest_src(int dst, float scale, int in_size) {
 }
 
 // item = (f, p, c8): 8 consecutive channels of one (frame, pixel)
+template <bool MAPPED>
 __global__ __launch_bounds__(256) void pnp_tokens_kernel(const PnpArgs p) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= p.total) return;
@@ -42,7 +59,7 @@ __global__ __launch_bounds__(256) void pnp_tokens_kernel(const PnpArgs p) {
   const int py = px / p.width, pxx = px - py * p.width;
   const int my = nearest_src(py, p.sy, p.mask_h), mx = nearest_src(pxx, p.sx, p.mask_w);
   const long off = (long)f * p.f_stride + (long)px * p.p_stride + c8 * 8;
-  const int nchunk = p.nobj + 1 + p.ndst;
+  const int nchunk = chunk_count<MAPPED>(p);
   const int basec = p.base_chunk0 ? 0 : nchunk - 1;
   const half8_t bv = *reinterpret_cast<const half8_t*>(x + basec * p.chunk_stride + off);
   float inj[8];
@@ -50,7 +67,7 @@ __global__ __launch_bounds__(256) void pnp_tokens_kernel(const PnpArgs p) {
   for (int e = 0; e < 8; ++e) inj[e] = (float)bv[e];
   for (int j = 0; j < p.nobj; ++j) {
     const float m = (float)p.masks[(((long)j * p.frames + f) * p.mask_h + my) * p.mask_w + mx];
-    const half8_t ov = *reinterpret_cast<const half8_t*>(x + (j + 1) * p.chunk_stride + off);
+    const half8_t ov = *reinterpret_cast<const half8_t*>(x + obj_chunk<MAPPED>(p, j) * p.chunk_stride + off);
 #pragma unroll
     for (int e = 0; e < 8; ++e) inj[e] = blend16(inj[e], (float)ov[e], m);
   }
@@ -62,7 +79,7 @@ __global__ __launch_bounds__(256) void pnp_tokens_kernel(const PnpArgs p) {
 }
 
 // NCHW: x [(nobj+3)*F, C, H, W]; item = (f, c, p8) with VEC consecutive pixels
-template <int VEC>
+template <int VEC, bool MAPPED>
 __global__ __launch_bounds__(256) void pnp_nchw_kernel(const PnpArgs p) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= p.total) return;
@@ -74,7 +91,7 @@ __global__ __launch_bounds__(256) void pnp_nchw_kernel(const PnpArgs p) {
   const int f = (int)(fc / p.channels);
   const long off = fc * hw + (long)pv * VEC;  // (f*C + c)*HW + p
   const long chunk = (long)p.frames * p.channels * hw;
-  const int nchunk = p.nobj + 1 + p.ndst;
+  const int nchunk = chunk_count<MAPPED>(p);
   const int basec = p.base_chunk0 ? 0 : nchunk - 1;
   float inj[VEC];
   half_t tmp[VEC];
@@ -87,9 +104,9 @@ __global__ __launch_bounds__(256) void pnp_nchw_kernel(const PnpArgs p) {
   for (int e = 0; e < VEC; ++e) inj[e] = (float)tmp[e];
   for (int j = 0; j < p.nobj; ++j) {
     if constexpr (VEC == 8) {
-      *reinterpret_cast<half8_t*>(tmp) = *reinterpret_cast<const half8_t*>(x + (j + 1) * chunk + off);
+      *reinterpret_cast<half8_t*>(tmp) = *reinterpret_cast<const half8_t*>(x + obj_chunk<MAPPED>(p, j) * chunk + off);
     } else {
-      tmp[0] = x[(j + 1) * chunk + off];
+      tmp[0] = x[obj_chunk<MAPPED>(p, j) * chunk + off];
     }
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
@@ -126,6 +143,26 @@ int fill_args(const mvoc_pnp_desc* d, PnpArgs& a) {
   a.ndst = d->ndst == 0 ? 2 : d->ndst;
   a.sy = (float)d->mask_h / (float)d->height;
   a.sx = (float)d->mask_w / (float)d->width;
+  a.nsrc = d->nobj + 1;
+  a.obj_map = 0;
+  return 0;
+}
+
+// source map of the _mapped entries -> a.nsrc / a.obj_map; returns the number of DISTINCT source chunks the blend reads (the
+// base included): repeated reads of one chunk hit the same lines back to back, so HBM serves each distinct chunk once
+int fill_map(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk_host, PnpArgs& a, int& nread) {
+  MVOC_REQUIRE(obj_chunk_host, -1, "pnp mapped: null obj_chunk");
+  MVOC_REQUIRE(nsrc >= 1 && nsrc <= d->nobj + 1, -1, "pnp mapped: nsrc %d not in [1, nobj + 1 = %d]", nsrc, d->nobj + 1);
+  unsigned map = 0, seen = d->base_chunk0 ? 1u : 0u;  // bit c: chunk c is read (the base when it is chunk 0)
+  for (int j = 0; j < d->nobj; ++j) {
+    const int c = obj_chunk_host[j];
+    MVOC_REQUIRE(c >= 0 && c < nsrc, -1, "pnp mapped: obj_chunk[%d] = %d not in [0, nsrc = %d)", j, c, nsrc);
+    map |= (unsigned)c << (4 * j);
+    seen |= 1u << c;
+  }
+  a.nsrc = nsrc;
+  a.obj_map = map;
+  nread = __builtin_popcount(seen) + (d->base_chunk0 ? 0 : 1);  // + the last chunk as the base
   return 0;
 }
 
@@ -178,9 +215,11 @@ __global__ __launch_bounds__(256) void fusion_kernel(const half_t* __restrict__ 
 
 }  // namespace
 
-extern "C" int mvoc_pnp_blend_scatter_tokens(const mvoc_pnp_desc* d, void* stream) {
-  PnpArgs a;
-  if (int rc = fill_args(d, a)) return rc;
+namespace {
+
+// nread: source chunks read from HBM (the base included); ndst chunks written
+template <bool MAPPED>
+int launch_tokens(const mvoc_pnp_desc* d, PnpArgs& a, int nread, void* stream) {
   MVOC_REQUIRE(d->channels % 8 == 0 && d->chunk_stride % 8 == 0 && d->f_stride % 8 == 0 && d->p_stride % 8 == 0, -2,
                "pnp tokens: channels/strides must be multiples of 8");
   a.total = (long)d->frames * d->height * d->width * (d->channels / 8);
@@ -189,14 +228,13 @@ extern "C" int mvoc_pnp_blend_scatter_tokens(const mvoc_pnp_desc* d, void* strea
   const int ntens = d->x2 ? 2 : 1;
   hipStream_t s = (hipStream_t)stream;
   const double elems = (double)d->frames * d->height * d->width * d->channels;
-  MvocProfScope prof(MVOC_FAM_PNP, s, ntens * (elems * 2.0 * (d->nobj + 1 + a.ndst) + 2.0 * d->nobj * d->frames * d->height * d->width));
-  hipLaunchKernelGGL(pnp_tokens_kernel, dim3((unsigned)nblk, ntens), dim3(256), 0, s, a);
+  MvocProfScope prof(MVOC_FAM_PNP, s, ntens * (elems * 2.0 * (nread + a.ndst) + 2.0 * d->nobj * d->frames * d->height * d->width));
+  hipLaunchKernelGGL(pnp_tokens_kernel<MAPPED>, dim3((unsigned)nblk, ntens), dim3(256), 0, s, a);
   return mvoc_check_launch("pnp_tokens_kernel");
 }
 
-extern "C" int mvoc_pnp_blend_scatter_nchw(const mvoc_pnp_desc* d, void* stream) {
-  PnpArgs a;
-  if (int rc = fill_args(d, a)) return rc;
+template <bool MAPPED>
+int launch_nchw(const mvoc_pnp_desc* d, PnpArgs& a, int nread, void* stream) {
   const long hw = (long)d->height * d->width;
   const bool vec = hw % 8 == 0;
   a.total = (long)d->frames * d->channels * (vec ? hw / 8 : hw);
@@ -205,12 +243,44 @@ extern "C" int mvoc_pnp_blend_scatter_nchw(const mvoc_pnp_desc* d, void* stream)
   const int ntens = d->x2 ? 2 : 1;
   hipStream_t s = (hipStream_t)stream;
   const double elems = (double)d->frames * hw * d->channels;
-  MvocProfScope prof(MVOC_FAM_PNP, s, ntens * (elems * 2.0 * (d->nobj + 1 + a.ndst) + 2.0 * d->nobj * d->frames * hw));
+  MvocProfScope prof(MVOC_FAM_PNP, s, ntens * (elems * 2.0 * (nread + a.ndst) + 2.0 * d->nobj * d->frames * hw));
   if (vec)
-    hipLaunchKernelGGL(pnp_nchw_kernel<8>, dim3((unsigned)nblk, ntens), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((pnp_nchw_kernel<8, MAPPED>), dim3((unsigned)nblk, ntens), dim3(256), 0, s, a);
   else
-    hipLaunchKernelGGL(pnp_nchw_kernel<1>, dim3((unsigned)nblk, ntens), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((pnp_nchw_kernel<1, MAPPED>), dim3((unsigned)nblk, ntens), dim3(256), 0, s, a);
   return mvoc_check_launch("pnp_nchw_kernel");
+}
+
+}  // namespace
+
+extern "C" int mvoc_pnp_blend_scatter_tokens(const mvoc_pnp_desc* d, void* stream) {
+  PnpArgs a;
+  if (int rc = fill_args(d, a)) return rc;
+  return launch_tokens<false>(d, a, d->nobj + 1, stream);
+}
+
+extern "C" int mvoc_pnp_blend_scatter_nchw(const mvoc_pnp_desc* d, void* stream) {
+  PnpArgs a;
+  if (int rc = fill_args(d, a)) return rc;
+  return launch_nchw<false>(d, a, d->nobj + 1, stream);
+}
+
+extern "C" int mvoc_pnp_blend_scatter_tokens_mapped(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
+                                                    void* stream) {
+  PnpArgs a;
+  int nread = 0;
+  if (int rc = fill_args(d, a)) return rc;
+  if (int rc = fill_map(d, nsrc, obj_chunk, a, nread)) return rc;
+  return launch_tokens<true>(d, a, nread, stream);
+}
+
+extern "C" int mvoc_pnp_blend_scatter_nchw_mapped(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
+                                                  void* stream) {
+  PnpArgs a;
+  int nread = 0;
+  if (int rc = fill_args(d, a)) return rc;
+  if (int rc = fill_map(d, nsrc, obj_chunk, a, nread)) return rc;
+  return launch_nchw<true>(d, a, nread, stream);
 }
 
 extern "C" int mvoc_ddim_step_f16(const void* x, const void* v_uncond, const void* v_cond, const float* coef_dev,

@@ -506,21 +506,39 @@ def _pnp_desc(x, x2, masks, chunk_stride, f_stride, p_stride, frames, height, wi
     return d
 
 
+def _src_map_args(src_map, nobj):
+    """``src_map`` = (nsrc, obj_chunks) of the source-de-duplicated batch [s_0..s_{nsrc-1}, destinations..] -> ctypes args"""
+    nsrc, chunks = src_map
+    if len(chunks) != nobj:
+        raise RuntimeError(f"pnp: the source map names {len(chunks)} objects, the masks {nobj}")
+    return int(nsrc), (C.c_int32 * nobj)(*[int(c) for c in chunks])
+
+
 def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride, f_stride, p_stride, x2=None,
-                     base_chunk0=False, ndst=2):
+                     base_chunk0=False, ndst=2, src_map=None):
     """In-place masked blend + scatter on channel-contiguous data (see include/mvoc_hip.h).  ``ndst``: trailing
-    destination chunks (2 = [uncond, cond], 1 = [cond] with CFG off)."""
+    destination chunks (2 = [uncond, cond], 1 = [cond] with CFG off).  ``src_map`` = (nsrc, obj_chunks): the batch holds
+    nsrc de-duplicated source chunks, object j reads chunk obj_chunks[j] (None: [bg, obj_1..obj_n], the unmapped entry)."""
     d = _pnp_desc(x, x2, masks, chunk_stride, f_stride, p_stride, frames, height, width, channels, base_chunk0, ndst)
-    check(lib.mvoc_pnp_blend_scatter_tokens(C.byref(d), _stream()), "pnp_blend_scatter_tokens")
+    if src_map is None:
+        check(lib.mvoc_pnp_blend_scatter_tokens(C.byref(d), _stream()), "pnp_blend_scatter_tokens")
+    else:
+        nsrc, chunks = _src_map_args(src_map, d.nobj)
+        check(lib.mvoc_pnp_blend_scatter_tokens_mapped(C.byref(d), nsrc, chunks, _stream()), "pnp_blend_scatter_tokens_mapped")
     return x
 
 
-def pnp_blend_nchw(x, masks, *, frames, x2=None, base_chunk0=True, ndst=2):
-    """In-place on x [(nobj+1+ndst)*F, C, H, W] (reference feature-map layout)."""
+def pnp_blend_nchw(x, masks, *, frames, x2=None, base_chunk0=True, ndst=2, src_map=None):
+    """In-place on x [(nobj+1+ndst)*F, C, H, W] (reference feature-map layout); with ``src_map`` = (nsrc, obj_chunks)
+    x is [(nsrc+ndst)*F, C, H, W] (see ``pnp_blend_tokens``)."""
     if x.dim() != 4 or not x.is_contiguous():
         raise RuntimeError("pnp_blend_nchw: x must be contiguous [N, C, H, W]")
     d = _pnp_desc(x, x2, masks, 0, 0, 0, frames, x.shape[2], x.shape[3], x.shape[1], base_chunk0, ndst)
-    check(lib.mvoc_pnp_blend_scatter_nchw(C.byref(d), _stream()), "pnp_blend_scatter_nchw")
+    if src_map is None:
+        check(lib.mvoc_pnp_blend_scatter_nchw(C.byref(d), _stream()), "pnp_blend_scatter_nchw")
+    else:
+        nsrc, chunks = _src_map_args(src_map, d.nobj)
+        check(lib.mvoc_pnp_blend_scatter_nchw_mapped(C.byref(d), nsrc, chunks, _stream()), "pnp_blend_scatter_nchw_mapped")
     return x
 
 

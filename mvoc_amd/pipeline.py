@@ -107,6 +107,55 @@ class SyntheticConditioner:
         return self.vae.decode(latents)
 
 
+SOURCE_COND_KEYS = ("encoder_hidden_states", "image_embeddings", "image_latents_first", "image_latents", "fps")
+
+
+def source_classes(cond, n_obj):
+    """Static partition of a composition batch's source roles (0 = background, j = object j) for source de-duplication:
+    role r joins the class of the first earlier role whose conditioning rows (``SOURCE_COND_KEYS``) equal its own bit for bit,
+    else starts its own.  -> tuple of class ids (the class's first role), one per role."""
+    classes = []
+    for r in range(n_obj + 1):
+        c = r
+        for q in range(r):
+            if classes[q] == q and all(torch.equal(cond[k][q], cond[k][r]) for k in SOURCE_COND_KEYS):
+                c = q
+                break
+        classes.append(c)
+    return tuple(classes)
+
+
+def plan_source_map(classes, latents):
+    """Per-step source map: roles of one class (``source_classes``) share a UNet chunk when they were handed the SAME latents
+    tensor object (``LatentCache.get`` returns one tensor per directory and t).  ``latents``: one object per role, background
+    first.  -> None when every role keeps its own chunk (the positional batch), else (nsrc, obj_chunks): chunks numbered in
+    the order of their first role, so the background is always chunk 0 and object j reads chunk obj_chunks[j]."""
+    if classes is None:
+        return None
+    if len(classes) != len(latents):
+        raise ValueError(f"plan_source_map: {len(classes)} roles classified, {len(latents)} latents")
+    firsts, chunk_of = [], []  # first role of each chunk
+    for r, lat in enumerate(latents):
+        for i, q in enumerate(firsts):
+            if classes[q] == classes[r] and latents[q] is lat:
+                chunk_of.append(i)
+                break
+        else:
+            chunk_of.append(len(firsts))
+            firsts.append(r)
+    if len(firsts) == len(latents):
+        return None
+    return len(firsts), tuple(chunk_of[1:])
+
+
+def source_rows(smap, n_obj):
+    """roles whose latents / conditioning rows fill the source chunks of ``smap`` (the first role of each chunk)"""
+    if smap is None:
+        return list(range(n_obj + 1))
+    nsrc, chunks = smap
+    return [0] + [1 + chunks.index(c) for c in range(1, nsrc)]
+
+
 class GraphedStep:
     """Capture one loop iteration (a python callable working on static device buffers) into a hipGraph."""
 
@@ -149,6 +198,10 @@ class I2VGenXLPipeline:
         self.prune_source_tail = os.environ.get("MVOC_PRUNE_SOURCE_TAIL", "1") != "0"  # (=0: A/B)
         # ... and its unconditional / conditional chunks are one computation up to the first cross-attention (unet.shared_prefix_chunks)
         self.share_cfg_prefix = os.environ.get("MVOC_SHARE_CFG_PREFIX", "1") != "0"  # (=0: A/B)
+        # ... and source roles that are the same source (same conditioning, same inversion latents) share one chunk: the batch
+        # [s_0..s_{k-1}, uncond, cond] (plan_source_map, unet.source_chunks).  Opt-in: MVOC_DEDUP_SOURCES=1 or composite.py
+        # --dedup_sources; the VAE draws of identical conditioning images are then shared too
+        self.dedup_sources = os.environ.get("MVOC_DEDUP_SOURCES", "0") != "0"
         self.latent_cache = LatentCache(unet.device)
 
     # ---- reference plumbing ------------------------------------------------------------------------
@@ -462,26 +515,27 @@ class I2VGenXLPipeline:
         return tensor2vid(self.conditioner.decode(latents), output_type)
 
     # ---- composition --------------------------------------------------------------------------------------
-    def make_composition_state(self, latents, cond, masks, guidance_scale):
+    def make_composition_state(self, latents, cond, masks, guidance_scale, dedup_sources=None):
         """static buffers + the captured iteration variants of the composition loop.
         cond: dict(encoder_hidden_states [n,77,D], image_embeddings [n,F,D], image_latents_first, image_latents, fps).
         The state keeps its OWN copy of ``cond``: the hoisted conditioning (``prepare_conditioning``) and the shared-CFG-prefix
         decision below are taken once from these values, so a caller that later rewrites its tensors in place cannot make the
-        captured iterations disagree with them -- new conditioning = a new state."""
+        captured iterations disagree with them -- new conditioning = a new state.
+        ``dedup_sources`` (None: ``self.dedup_sources``): classify the source roles once (``source_classes``); every step then
+        runs the batch its source map (``plan_source_map``) lays out, each map with its own buffers, built on first use."""
         cond = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in cond.items()}
         n_obj = len(masks)
         do_cfg = guidance_scale > 1  # off: batch [bg, objs.., cond], one destination chunk for the injections (SURVEY 8f-4)
         nb = n_obj + (3 if do_cfg else 2)
         dev = self.device
+        dedup = self.dedup_sources if dedup_sources is None else bool(dedup_sources)
         st = {"latents": latents.clone(), "inp": torch.empty((nb,) + tuple(latents.shape[1:]), dtype=H16, device=dev),
               "t": torch.zeros(1, dtype=torch.float32, device=dev), "coef": torch.zeros(5, dtype=torch.float32, device=dev),
               "masks": masks, "variants": {}, "cond": cond, "n_obj": n_obj,
               "fusion_masks": torch.stack([m[0].to(dev, H16) for m in masks]).contiguous(),
-              "fusion_objs": torch.empty((n_obj,) + tuple(latents.shape), dtype=H16, device=dev)}
-
-        prepared = self.unet.prepare_conditioning(tuple(st["inp"].shape), cond["fps"], cond["image_latents_first"],
-                                                  cond["image_latents"], cond["image_embeddings"],
-                                                  cond["encoder_hidden_states"], False)
+              "fusion_objs": torch.empty((n_obj,) + tuple(latents.shape), dtype=H16, device=dev), "maps": {}}
+        st["build_map"] = lambda smap: self._composition_batch(st, smap, do_cfg)
+        st["maps"][None] = st["build_map"](None)
 
         # classifier-free guidance: the unconditional and the conditional chunk receive the same latent (below); when their image
         # latents and fps are equal too -- the reference builds both from the main image, pipeline_i2vgen_xl.py:1676-1690 -- they
@@ -489,54 +543,79 @@ class I2VGenXLPipeline:
         share = bool(self.share_cfg_prefix and do_cfg and
                      all(torch.equal(cond[k][nb - 2], cond[k][nb - 1]) for k in ("image_latents_first", "image_latents", "fps")))
         st["share_cfg_prefix"] = share
+        # (a frame-sharded clip runs the full layout: no de-duplication)
+        st["classes"] = source_classes(cond, n_obj) if dedup and self.unet.shard is None else None
+        st["body"] = st["maps"][None]["body"]
+        st["nb"] = nb
+        return st
+
+    def _composition_batch(self, st, smap, do_cfg):
+        """the UNet batch of one source map (None: the positional [bg, obj_1..obj_n, (uncond,) cond]): its input buffer, its
+        rows of the conditioning, the hoisted conditioning and the iteration body"""
+        n_obj, cond = st["n_obj"], st["cond"]
+        if smap is None:
+            inp, mcond = st["inp"], cond
+        else:
+            nb_full = n_obj + (3 if do_cfg else 2)
+            rows = torch.tensor(source_rows(smap, n_obj) + list(range(n_obj + 1, nb_full)), device=self.device)
+            mcond = {k: v.index_select(0, rows.to(v.device)).contiguous() for k, v in cond.items()}
+            inp = torch.empty((len(rows),) + tuple(st["latents"].shape[1:]), dtype=H16, device=self.device)
+        nb = inp.shape[0]
+        prepared = self.unet.prepare_conditioning(tuple(inp.shape), mcond["fps"], mcond["image_latents_first"],
+                                                  mcond["image_latents"], mcond["image_embeddings"],
+                                                  mcond["encoder_hidden_states"], False)
 
         def body():
             x = st["latents"]
             if do_cfg:
-                st["inp"][nb - 2].copy_(x[0])
-            st["inp"][nb - 1].copy_(x[0])
+                inp[nb - 2].copy_(x[0])
+            inp[nb - 1].copy_(x[0])
             u = self.unet
             saved, u.prune_source_tail = u.prune_source_tail, bool(self.prune_source_tail)  # this loop reads the destination chunks only
-            saved_sp, u.shared_prefix_chunks = u.shared_prefix_chunks, (2 if share else 0)
+            saved_sp, u.shared_prefix_chunks = u.shared_prefix_chunks, (2 if st["share_cfg_prefix"] else 0)
+            saved_sc, u.source_chunks = u.source_chunks, smap
             try:
-                noise = u.forward_ext(st["inp"], st["t"], cond["fps"], cond["image_latents_first"], cond["image_latents"],
-                                      cond["image_embeddings"], cond["encoder_hidden_states"], multi_frame_guidance=False,
+                noise = u.forward_ext(inp, st["t"], mcond["fps"], mcond["image_latents_first"], mcond["image_latents"],
+                                      mcond["image_embeddings"], mcond["encoder_hidden_states"], multi_frame_guidance=False,
                                       conditioning=prepared)[0]
             finally:
-                u.prune_source_tail, u.shared_prefix_chunks = saved, saved_sp
+                u.prune_source_tail, u.shared_prefix_chunks, u.source_chunks = saved, saved_sp, saved_sc
             ops.ddim_step(x, noise[nb - 1:nb].contiguous(), st["coef"],
                           v_uncond=noise[nb - 2:nb - 1].contiguous() if do_cfg else None, out=x)
 
-        st["body"] = body
-        st["nb"] = nb
-        return st
+        return {"inp": inp, "cond": mcond, "prepared": prepared, "body": body, "nb": nb}
 
     def composition_step(self, st, t, bg_latents, obj_latents, table_row, fuse=None):
         """one iteration of ``:1636-1734`` on device-resident latents; ``fuse`` = (mix_ratio, obj_random_noise_fusion,
-        fusion object latents) on fusion steps"""
+        fusion object latents) on fusion steps.  With source de-duplication the roles handed the same latents tensor (and of
+        one conditioning class) share a chunk: the step's source map picks the batch."""
         if fuse is not None:
             mix, rnf, fobjs = fuse
             for j, o in enumerate(fobjs):
                 st["fusion_objs"][j].copy_(o)
             ops.latent_fusion(st["latents"], bg_latents, st["fusion_objs"], st["fusion_masks"], mix, rnf, out=st["latents"])
             obj_latents = fobjs
-        st["inp"][0].copy_(bg_latents[0])
-        for j, o in enumerate(obj_latents):
-            st["inp"][1 + j].copy_(o[0])
+        smap = plan_source_map(st.get("classes"), [bg_latents] + list(obj_latents))
+        b = st["maps"].get(smap)
+        if b is None:
+            b = st["maps"][smap] = st["build_map"](smap)
+        src = [bg_latents] + list(obj_latents)
+        for c, r in enumerate(source_rows(smap, st["n_obj"])):
+            b["inp"][c].copy_(src[r][0])
         st["t"].fill_(float(t))
         st["coef"].copy_(table_row)
         register_time_all(self, int(t), st["masks"])
         if not self.use_graphs:
-            st["body"]()
+            b["body"]()
             return
-        # a captured iteration bakes in EVERY site's injecting() decision (the reference allows a schedule per site) and
-        # the device copies of the masks: both are part of the variant key
+        # a captured iteration bakes in EVERY site's injecting() decision (the reference allows a schedule per site), the
+        # device copies of the masks and the batch's source map: all are part of the variant key
         u = self.unet
         vkey = (u.injection_flags(), u.mask_key(st["masks"]), bool(u.pair_destinations), bool(u.prune_dead_chunks),
-                bool(self.prune_source_tail), bool(st.get("share_cfg_prefix")))
+                bool(self.prune_source_tail), bool(st.get("share_cfg_prefix")), smap)
         g = st["variants"].get(vkey)
         if g is None:
-            g = st["variants"][vkey] = GraphedStep(st["body"], preserve=(st["latents"],))
+            g = st["variants"][vkey] = GraphedStep(b["body"], preserve=(st["latents"],))
         g()
 
     @torch.no_grad()
@@ -560,23 +639,48 @@ class I2VGenXLPipeline:
         c = self.conditioner
         n_obj = len(obj_ddim_latents_path)
         assert obj_mask is None or len(obj_mask) == n_obj
+        # source de-duplication: roles showing the same image share ONE draw of the VAE posterior (prepare_image_latents samples
+        # per role, :860-890) and one vision-tower pass -- else identical frames would give every role its own image latents and
+        # no two roles could share a chunk (make_composition_state)
+        dedup = bool(self.dedup_sources)
+        memo = {}
+
+        def image_latents(image):
+            if not dedup:
+                return c.image_latents(image, num_frames, height, width)
+            k = SyntheticConditioner._image_key(image)
+            if k not in memo:
+                memo[k] = c.image_latents(image, num_frames, height, width)
+            return memo[k]
+
+        def encode_frames(frames):
+            # (a conditioner without the batched entry -- the documented interface is encode_image -- is called per frame)
+            return c.encode_images(frames) if hasattr(c, "encode_images") else torch.cat([c.encode_image(f) for f in frames])
         # conditioning, assembled in the reference's batch order [bg, obj_1.., uncond, cond] (:1387, 1476, 1498, 1540)
         pe, ne = (prompt_embeds, negative_prompt_embeds) if prompt_embeds is not None else c.encode_prompt(prompt, negative_prompt)
         inv_pe, _ = c.encode_prompt(ddim_inv_prompt, negative_prompt)
         ehs = torch.cat([inv_pe.repeat(n_obj + 1, 1, 1)] + ([ne] if do_cfg else []) + [pe])
-        main_lat = c.image_latents(main_first_image, num_frames, height, width)
-        bg_lat = c.image_latents(background_first_image, num_frames, height, width)
-        obj_first = [c.image_latents(im, num_frames, height, width) for im in objs_first_image]
+        main_lat = image_latents(main_first_image)
+        bg_lat = image_latents(background_first_image)
+        obj_first = [image_latents(im) for im in objs_first_image]
         first_all = torch.cat([bg_lat] + obj_first + [main_lat] * (2 if do_cfg else 1))
-        obj_lat = [c.image_latents(frames[0], num_frames, height, width) for frames in objs_image_list]
-        bg_lat2 = c.image_latents(background_image_list[0], num_frames, height, width)
+        obj_lat = [image_latents(frames[0]) for frames in objs_image_list]
+        bg_lat2 = image_latents(background_image_list[0])
         lat_all = torch.cat([bg_lat2] + obj_lat + [main_lat] * (2 if do_cfg else 1))
 
         # every conditioning frame of the job (background, objects, main: 4 x 16 in the demo) through the vision tower at once
         lists = [background_image_list] + list(objs_image_list) + [main_image_list]
         allf = [f for fr in lists for f in fr]
-        # (a conditioner without the batched entry -- the documented interface is encode_image -- is called per frame)
-        flat = c.encode_images(allf) if hasattr(c, "encode_images") else torch.cat([c.encode_image(f) for f in allf])  # [sum F, 1, 1024]
+        if dedup:  # each distinct frame once, then gathered back into every list that shows it
+            keys = [SyntheticConditioner._image_key(f) for f in allf]
+            uniq = {}
+            for k, f in zip(keys, allf):
+                uniq.setdefault(k, f)
+            pos = {k: i for i, k in enumerate(uniq)}
+            uflat = encode_frames(list(uniq.values()))
+            flat = uflat[torch.tensor([pos[k] for k in keys], device=uflat.device)]
+        else:
+            flat = encode_frames(allf)  # [sum F, 1, 1024]
         embs, o = [], 0
         for fr in lists:
             embs.append(flat[o:o + len(fr)].transpose(0, 1))  # [1, F, 1024]

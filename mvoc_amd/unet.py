@@ -327,11 +327,11 @@ class Transformer2DModel(_TransformerBase):
         proc = blk.attn1.processor
         ndst = 0
         if proc.injecting() and not eng._pruned:
-            ndst = eng.check_pnp_batch(B, proc.mask)
+            ndst, smap = eng.pnp_batch(B, proc.mask)
             masks = eng.device_masks(proc.mask)[1]  # bool masks as {0,1} fp16
             ld = qkv.stride(0)
             ops.pnp_blend_tokens(q, masks, x2=k, frames=F, height=H, width=W, channels=c, chunk_stride=F * hw * ld,
-                                 f_stride=hw * ld, p_stride=ld, base_chunk0=proc.inject_background, ndst=ndst)
+                                 f_stride=hw * ld, p_stride=ld, base_chunk0=proc.inject_background, ndst=ndst, src_map=smap)
         if ndst == 2 and eng.pair_destinations:
             # the injection has just written ONE blended q / k into both destination chunks (pnp_utils.py:664-668): their
             # softmax(q k^T) is the same matrix -- computed once, multiplied into the two chunks' own v (bit-identical outputs)
@@ -398,11 +398,12 @@ class TransformerTemporalModel(_TransformerBase):
             qkv = attn.to_qkv.call_ln(h, norm)
             q, k, v = qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:]
             if inject:
-                ndst = eng.check_pnp_batch(B, proc.mask)
+                ndst, smap = eng.pnp_batch(B, proc.mask)
                 masks = eng.section_masks(proc.mask, 0, full_hw)  # soft float masks, channel 0
                 ld = qkv.stride(0)
                 ops.pnp_blend_tokens(q, masks, x2=k, frames=F, height=H, width=W, channels=c, chunk_stride=F * hw * ld,
-                                     f_stride=hw * ld, p_stride=ld, base_chunk0=proc.inject_background, ndst=ndst)
+                                     f_stride=hw * ld, p_stride=ld, base_chunk0=proc.inject_background, ndst=ndst,
+                                     src_map=smap)
                 if eng._tail_site is self:  # (prune_source_tail) the last reader of the source chunks was this blend
                     r0 = (B - ndst) * F * hw
                     q, k, v, h, x = q[r0:], k[r0:], v[r0:], h[r0:], x[r0:]
@@ -605,6 +606,12 @@ class I2VGenXLUNet:
         # Q/K-injection sites: the two destination chunks attend with identical q and k (the hook assigns one blend to both);
         # their attention probabilities are computed once (ops.flash_attn v2 / out2).  False: five independent passes (A/B, tests)
         self.pair_destinations = True
+        # Source de-duplication (pipeline.py dedup_sources): None = the positional batch [bg, obj_1..obj_n, (uncond,) cond];
+        # (nsrc, obj_chunks) = the batch [s_0..s_{nsrc-1}, (uncond,) cond] in which roles that are the same source share one
+        # chunk -- chunk 0 is the background's, object j reads chunk obj_chunks[j].  Every injection site passes the map to the
+        # blend kernel.  Set and restored around its forward by the composition loop, like shared_prefix_chunks; the identity
+        # map is today's path.  Not with a frame shard.
+        self.source_chunks = None
 
     def set_frame_shard(self, shard):
         """Frame-shard every forward over the ranks of ``shard`` (``mvoc_amd.frame_shard``): each rank receives the FULL
@@ -734,16 +741,42 @@ class I2VGenXLUNet:
 
     # ---- PnP helpers ------------------------------------------------------------------------------
     @staticmethod
-    def check_pnp_batch(B, mask_list):
+    def check_pnp_batch(B, mask_list, nsrc=None):
         """the hooks address chunks positionally [bg, obj_1..obj_n, uncond, cond] (pnp_utils.py:592 hard-codes 5); with
-        classifier-free guidance off the batch is [bg, obj_1..obj_n, cond].  Returns the number of
-        trailing destination chunks (2 or 1)."""
-        if mask_list is None or B - len(mask_list) - 1 not in (1, 2):
-            raise RuntimeError(f"PnP injection is active but the UNet batch is {B}, expected n_objects+3 = "
-                               f"{None if mask_list is None else len(mask_list) + 3} ([bg, objects.., uncond, cond]) or "
-                               "n_objects+2 with guidance off; "
-                               "clear the hook state (register_time_all(pipe, None, None)) before non-composition calls")
-        return B - len(mask_list) - 1
+        classifier-free guidance off the batch is [bg, obj_1..obj_n, cond].  ``nsrc``: the number of source
+        chunks of a source-de-duplicated batch (``source_chunks``; None = n_objects + 1).  Returns the number of trailing
+        destination chunks (2 or 1)."""
+        if nsrc is None:
+            if mask_list is None or B - len(mask_list) - 1 not in (1, 2):
+                raise RuntimeError(f"PnP injection is active but the UNet batch is {B}, expected n_objects+3 = "
+                                   f"{None if mask_list is None else len(mask_list) + 3} ([bg, objects.., uncond, cond]) or "
+                                   "n_objects+2 with guidance off; "
+                                   "clear the hook state (register_time_all(pipe, None, None)) before non-composition calls")
+            return B - len(mask_list) - 1
+        if mask_list is None or B - nsrc not in (1, 2):
+            raise RuntimeError(f"PnP injection is active but the UNet batch is {B}, expected the {nsrc} de-duplicated source "
+                               f"chunks + 2 ([s_0..s_{nsrc - 1}, uncond, cond]) or + 1 with guidance off")
+        return B - nsrc
+
+    def pnp_src_map(self):
+        """the source map the injection sites pass to the blend kernels: ``source_chunks``, None for the positional batch
+        (also for the identity map: the unmapped entry points, today's launches)"""
+        sc = self.source_chunks
+        if sc is None:
+            return None
+        if self.shard is not None:
+            raise RuntimeError("source de-duplication (source_chunks) does not combine with the frame shard: run the full layout")
+        nsrc, chunks = int(sc[0]), tuple(int(c) for c in sc[1])
+        if nsrc == len(chunks) + 1 and chunks == tuple(range(1, nsrc)):
+            return None
+        return nsrc, chunks
+
+    def pnp_batch(self, B, mask_list):
+        """(ndst, source map) of an injection site's batch of B chunks (``check_pnp_batch`` under ``source_chunks``)"""
+        smap = self.pnp_src_map()
+        if smap is not None and len(smap[1]) != len(mask_list):
+            raise RuntimeError(f"source_chunks maps {len(smap[1])} objects, the hooks carry {len(mask_list)} masks")
+        return self.check_pnp_batch(B, mask_list, None if smap is None else smap[0]), smap
 
     def device_masks(self, mask_list):
         """list of (float [1,4,F,h,w], bool [1,4,F,h,w]) pairs (``register_time_all``'s ``mask``) ->
@@ -804,7 +837,7 @@ class I2VGenXLUNet:
         """feature injection (``pnp_utils.py:970-1004, 1059-1082, 1114-1146``): base = chunk 0, bool mask, no resize.
         ``full_hw`` is given by temporal sections (see ``section_masks``); elsewhere the rows are whole local frames."""
         B, F, H, W = geo
-        ndst = self.check_pnp_batch(B, mask_list)
+        ndst, smap = self.pnp_batch(B, mask_list)
         hard = self._all_frame_masks(mask_list)[1]
         fh, fw = full_hw if full_hw is not None else (H, W)
         if hard.shape[2] != fh or hard.shape[3] != fw:
@@ -813,7 +846,7 @@ class I2VGenXLUNet:
         hard = self.section_masks(mask_list, 1, full_hw) if full_hw is not None else self.device_masks(mask_list)[1]
         ld = h.stride(0)
         ops.pnp_blend_tokens(h, hard, frames=F, height=H, width=W, channels=channels, chunk_stride=F * H * W * ld,
-                             f_stride=H * W * ld, p_stride=ld, base_chunk0=True, ndst=ndst)
+                             f_stride=H * W * ld, p_stride=ld, base_chunk0=True, ndst=ndst, src_map=smap)
         if getattr(h, "chan_sums", None) is not None:
             h.chan_sums = None  # rewritten in place: the producer's GroupNorm statistics no longer describe these rows
 
@@ -954,10 +987,11 @@ class I2VGenXLUNet:
     def _forward_source_chunks(self, sample, timestep, fps, image_latents_first, image_latents, image_embeddings,
                                encoder_hidden_states, multi_frame_guidance, conditioning):
         """a conv_out-injection step (see ``prune_dead_chunks``): the network on the source chunks [bg, obj_1..obj_n] only,
-        then the reference's conv_out blend (``pnp_utils.py:1114-1146``) writes the destination chunks from them"""
+        then the reference's conv_out blend (``pnp_utils.py:1114-1146``) writes the destination chunks from them (with
+        ``source_chunks`` the sources are the de-duplicated chunks s_0..s_{nsrc-1}, possibly a single one)"""
         B, C, F, H, W = sample.shape
         co = self.conv_out
-        ndst = self.check_pnp_batch(B, co.mask)
+        ndst, smap = self.pnp_batch(B, co.mask)
         ns = B - ndst
         cut = lambda t, per=1: None if t is None else (t if (not torch.is_tensor(t)) or t.dim() == 0 or t.shape[0] != B * per
                                                        else t[:ns * per])
@@ -980,7 +1014,7 @@ class I2VGenXLUNet:
             self._pruned = False
         nchw = torch.empty((B * F, C, H, W), dtype=H16, device=self.device)
         nchw[:ns * F] = src.permute(0, 2, 1, 3, 4).reshape(ns * F, C, H, W)
-        ops.pnp_blend_nchw(nchw, self.device_masks(co.mask)[1], frames=F, base_chunk0=True, ndst=ndst)
+        ops.pnp_blend_nchw(nchw, self.device_masks(co.mask)[1], frames=F, base_chunk0=True, ndst=ndst, src_map=smap)
         return nchw.reshape(B, F, C, H, W).permute(0, 2, 1, 3, 4).contiguous()
 
     def spatial_transformers(self):
@@ -1095,12 +1129,12 @@ class I2VGenXLUNet:
                           silu=True)
         y, _, _ = ops.conv3x3(h, co.w, co.b, nimg=B * F, h=H, wd=W, n_store=co.cout)
         if co.injecting() and not self._pruned:
-            ndst = self.check_pnp_batch(B, co.mask)
+            ndst, smap = self.pnp_batch(B, co.mask)
             # conv_out writes cout (4) channels into a [rows, 4] buffer: the token kernel needs channels % 8 == 0,
             # so this tiny tensor goes through the NCHW form of the kernel on the boundary layout instead
             out = ops.tokens_to_ncfhw(y, B, co.cout, F, H, W)  # [B,C,F,h,w]
             nchw = out.permute(0, 2, 1, 3, 4).reshape(B * F, co.cout, H, W).contiguous()
-            ops.pnp_blend_nchw(nchw, self.device_masks(co.mask)[1], frames=F, base_chunk0=True, ndst=ndst)
+            ops.pnp_blend_nchw(nchw, self.device_masks(co.mask)[1], frames=F, base_chunk0=True, ndst=ndst, src_map=smap)
             out = nchw.reshape(B, F, co.cout, H, W).permute(0, 2, 1, 3, 4).contiguous()
         else:
             out = ops.tokens_to_ncfhw(y, B, co.cout, F, H, W)

@@ -11,6 +11,12 @@ architectures (MVOC_SYNTHETIC_VAE=1, MVOC_SYNTHETIC_CLIP=1), files written exact
 CLIP / file entry points with synchronising timers (IO excluded from the metric and reported separately).
 
 Used by `bench.py --workload demo`; prints one JSON object.  usage: python tools/demo_job.py [--frames 16] [--size 512] [--steps 50]
+
+--shared-source (opt-in): the shape of MVOC's own demo entries, where the background and both objects point at ONE inversion
+directory and the same control frames.  One clip is inverted, then the composition runs with source de-duplication off and then
+on (composite.py --dedup_sources), in this process; the JSON line holds both composition-stage times (the sampling call without
+the VAE decode, graph capture included), the speedup and the rel-L2 between the two final latents -- informational: with
+de-duplication the roles also share their VAE draws.
 """
 import argparse
 import json
@@ -78,7 +84,7 @@ def write_tree(root, frames, size):
             Image.fromarray(m).save(os.path.join(md, f"{i:05d}.png"))
 
 
-def run(frames=16, size=512, steps=50, keep=False):
+def _import_drivers():
     os.environ["MVOC_SYNTHETIC_VAE"] = os.environ["MVOC_SYNTHETIC_CLIP"] = "1"
     sys.path[:0] = [os.path.join(REPO, "i2vgen-xl"), REPO]
     for m in ("utils", "pnp_utils", "inverse", "composite", "pipelines", "pipelines.pipeline_i2vgen_xl"):
@@ -86,6 +92,11 @@ def run(frames=16, size=512, steps=50, keep=False):
     import composite
     import inverse
     import utils as ref_utils
+    return composite, inverse, ref_utils
+
+
+def run(frames=16, size=512, steps=50, keep=False):
+    composite, inverse, ref_utils = _import_drivers()
     from mvoc_amd.config import OmegaConf
     from mvoc_amd import latent_cache, pipeline as pl
     root = tempfile.mkdtemp(prefix="mvoc_demo_")
@@ -169,12 +180,96 @@ def run(frames=16, size=512, steps=50, keep=False):
     }
 
 
+def run_shared_source(frames=16, size=512, steps=50, keep=False):
+    """one inverted clip behind the background and both objects: the composition with source de-duplication off, then on"""
+    composite, inverse, _ = _import_drivers()
+    from mvoc_amd.config import OmegaConf
+    from mvoc_amd import pipeline as pl
+    root = tempfile.mkdtemp(prefix="mvoc_demo_shared_")
+    write_tree(root, frames, size)
+    dev = torch.device("cuda:0")
+    it = OmegaConf.load(os.path.join(REPO, "tests", "data", "inversion_template.yaml"))
+    it.data_dir = root
+    it.image_size = [size, size]
+    it.n_frames = frames
+    it.inverse_config.n_steps = steps
+    inverse.main(it, [{"active": True, "force_recompute_latents": True, "video_name": "bg_clip",
+                       "video_dir": os.path.join(root, "demo", "bg_clip"), "recon_config": {"enable_recon": False}}], dev, synthetic=True)
+    torch.cuda.synchronize()
+
+    # the sampling call's wall-clock without the VAE decode, and the final latents it decodes
+    rec = {"sample_s": 0.0, "decode_s": 0.0, "latents": None}
+    sample_name = "sample_with_pnp_pipeline_with_edit_prompt_extraction_with_attn_injection"
+    sample_fn, to_video = getattr(pl.I2VGenXLPipeline, sample_name), pl.I2VGenXLPipeline._to_video
+
+    def timed_sample(self, *a, **kw):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        try:
+            return sample_fn(self, *a, **kw)
+        finally:
+            torch.cuda.synchronize()
+            rec["sample_s"] += time.perf_counter() - t0
+
+    def timed_decode(self, latents, output_type):
+        rec["latents"] = latents.float().clone()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        try:
+            return to_video(self, latents, output_type)
+        finally:
+            torch.cuda.synchronize()
+            rec["decode_s"] += time.perf_counter() - t0
+
+    ct = OmegaConf.load(os.path.join(REPO, "tests", "data", "composite_template.yaml"))
+    ct.data_dir = root
+    ct.image_size = [size, size]
+    ct.n_frames = frames
+    ct.n_steps = steps
+    lat = "inversions/i2vgen-xl/bg_clip/ddim_latents"
+    clip = "demo/bg_clip/bg_clip"
+    centry = {"active": True, "task_name": "demo", "video_name": "bg_clip", "editing_prompt": "windsurf,sailboat,sky,ocean",
+              "editing_negative_prompt": "Chaotic, chaotic colors", "edited_video_name": "out",
+              "edited_first_frame_path": "demo/bg_clip/edited_first_frame/00000.png",
+              "ddim_init_latents_t_idx": 0, "pnp_f_t": 0.1, "pnp_spatial_attn_t": 1.0, "pnp_temp_attn_t": 1.0, "random_noise_ratio": 0.0,
+              "fusion_step": [0, 1], "obj_mask_path": ["demo/bg_clip/m1", "demo/bg_clip/m2"], "obj_width_height": [[size, size], [size, size]],
+              "obj_ddim_latents_path": [lat, lat], "bg_ddim_latents_path": lat,
+              "edited_contorl_frame_path_main": clip, "edited_contorl_frame_path_background": clip,
+              "edited_contorl_frame_path": [clip, clip]}
+    res = {}
+    setattr(pl.I2VGenXLPipeline, sample_name, timed_sample)
+    pl.I2VGenXLPipeline._to_video = timed_decode
+    try:
+        for name, dedup in (("off", False), ("on", True)):
+            rec.update(sample_s=0.0, decode_s=0.0, latents=None)
+            composite.main(ct, [centry], dev, synthetic=True, dedup_sources=dedup)
+            res[name] = (rec["sample_s"] - rec["decode_s"], rec["latents"])
+    finally:
+        setattr(pl.I2VGenXLPipeline, sample_name, sample_fn)
+        pl.I2VGenXLPipeline._to_video = to_video
+    if not keep:
+        shutil.rmtree(root, ignore_errors=True)
+    (t_off, l_off), (t_on, l_on) = res["off"], res["on"]
+    return {
+        "job": f"1 x {steps}-step DDIM inversion ({frames} frames, {size}x{size}) + 2 x {steps}-step PnP composition (bg + 2 objects, "
+               f"all three roles on that one source), composite.py without and with --dedup_sources, seeded synthetic weights",
+        "composition_s_dedup_off": round(t_off, 3), "composition_s_dedup_on": round(t_on, 3),
+        "speedup": round(t_off / t_on, 3),
+        "final_latents_rel_l2": float((l_on - l_off).norm() / l_off.norm()),
+        "note": "composition stage = the sampling call without the VAE decode (conditioning encoders, graph capture and the "
+                "denoising loop); the rel-L2 is informational: with de-duplication the roles also share their VAE draws",
+    }
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--keep", action="store_true")
+    ap.add_argument("--shared-source", action="store_true",
+                    help="one source behind every role: the composition without and with source de-duplication")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
-    print(json.dumps(run(a.frames, a.size, a.steps, a.keep)), flush=True)
+    fn = run_shared_source if a.shared_source else run
+    print(json.dumps(fn(a.frames, a.size, a.steps, a.keep)), flush=True)
