@@ -7,6 +7,8 @@ keys, hook registration order and output naming as the reference's ``i2vgen-xl/c
                                       [--dedup_sources]
 
 ``--dedup_sources``: roles (background, objects) that are the same source share one UNet chunk.
+An entry with ``variants: [{...}, ...]`` composes K prompts / seeds / guidance scales over its sources in one loop
+(``merge_variants``; files under ``.../variant_00/``, ``variant_01/`` ...).
 """
 import argparse
 import json
@@ -61,6 +63,62 @@ def output_suffix(config):
             + f"{config.fusion_step[0]}-{config.fusion_step[1]}")
 
 
+# what one variant of an entry may override; every other key is shared by the variants of a call (sources, masks, schedules,
+# fusion settings: the source chunks are computed once for all of them)
+VARIANT_KEYS = ("editing_prompt", "editing_negative_prompt", "seed", "cfg", "edited_first_frame_path",
+                "edited_contorl_frame_path_main")
+MAX_VARIANTS = 8
+
+
+def resolve_config(template_config, entry):
+    """template + entry, paths resolved against ``data_dir`` (``composite.py:88-110``)"""
+    config = OmegaConf.merge(template_config, OmegaConf.create(entry))
+    d = config.data_dir
+    config.video_path = os.path.join(config.video_dir, config.video_name + ".mp4")
+    config.video_frames_path = os.path.join(config.video_dir, config.video_name)
+    config.edited_first_frame_path = os.path.join(d, config.edited_first_frame_path)
+    config.obj_mask_path = [os.path.join(d, p) for p in config.obj_mask_path]
+    config.obj_ddim_latents_path = [os.path.join(d, p) for p in config.obj_ddim_latents_path]
+    config.bg_ddim_latents_path = os.path.join(d, config.bg_ddim_latents_path)
+    config.edited_contorl_frame_path_main = os.path.join(d, config.edited_contorl_frame_path_main)
+    config.edited_contorl_frame_path_background = os.path.join(d, config.edited_contorl_frame_path_background)
+    config.edited_contorl_frame_path = [os.path.join(d, p) for p in config.edited_contorl_frame_path]
+    return config
+
+
+def merge_variants(template_config, entry):
+    """An entry may carry ``variants: [{...}, ...]``: K compositions over the entry's sources in one loop, each dict overriding
+    any of ``VARIANT_KEYS``.  -> (config, None) for an entry without the key -- exactly the single composition -- else
+    (the entry's own config, [merged config of variant k]).  Overriding a shared key is an error that names it."""
+    entry = dict(entry)
+    variants = entry.pop("variants", None)
+    config = resolve_config(template_config, entry)
+    if variants is None:
+        return config, None
+    if not 1 <= len(variants) <= MAX_VARIANTS:
+        raise ValueError(f"variants: {len(variants)} entries, 1 to {MAX_VARIANTS} share one set of sources")
+    merged = []
+    for k, v in enumerate(variants):
+        for key in v:
+            if key not in VARIANT_KEYS:
+                raise ValueError(f"variants[{k}] overrides '{key}', which all variants of an entry share; a variant may set "
+                                 f"{', '.join(VARIANT_KEYS)}")
+        merged.append(resolve_config(template_config, {**entry, **dict(v)}))
+    return config, merged
+
+
+def variant_output_dir(config, k):
+    """``<output_dir>/<output_suffix of the variant's merged config>/variant_{k:02d}``"""
+    return os.path.join(config.output_dir, output_suffix(config), f"variant_{k:02d}")
+
+
+def _write_video(video, config, output_dir):
+    video = [f.resize(tuple(config.image_size), resample=Image.LANCZOS) for f in video]
+    export_to_gif(video, os.path.join(output_dir, "video.gif"))
+    for i, f in enumerate(video):
+        f.save(os.path.join(output_dir, f"video_{i:05d}.png"))
+
+
 def main(template_config, configs_list, device, synthetic=False, dedup_sources=False):
     from inverse import build_pipeline
     pipe = build_pipeline(device, synthetic)
@@ -70,19 +128,11 @@ def main(template_config, configs_list, device, synthetic=False, dedup_sources=F
     for entry in configs_list:
         if not entry["active"]:
             continue
-        config = OmegaConf.merge(template_config, OmegaConf.create(entry))
-        d = config.data_dir
-        config.video_path = os.path.join(config.video_dir, config.video_name + ".mp4")
-        config.video_frames_path = os.path.join(config.video_dir, config.video_name)
-        config.edited_first_frame_path = os.path.join(d, config.edited_first_frame_path)
-        config.obj_mask_path = [os.path.join(d, p) for p in config.obj_mask_path]
-        config.obj_ddim_latents_path = [os.path.join(d, p) for p in config.obj_ddim_latents_path]
-        config.bg_ddim_latents_path = os.path.join(d, config.bg_ddim_latents_path)
-        config.edited_contorl_frame_path_main = os.path.join(d, config.edited_contorl_frame_path_main)
-        config.edited_contorl_frame_path_background = os.path.join(d, config.edited_contorl_frame_path_background)
-        config.edited_contorl_frame_path = [os.path.join(d, p) for p in config.edited_contorl_frame_path]
+        config, variants = merge_variants(template_config, entry)
         logger.info(f"config: {OmegaConf.to_yaml(config)}")
-        main_1st = load_image(config.edited_first_frame_path).resize(tuple(config.image_size), resample=Image.Resampling.LANCZOS)
+        size = tuple(config.image_size)
+        first = lambda c: load_image(c.edited_first_frame_path).resize(size, resample=Image.Resampling.LANCZOS)
+        main_1st = first(config)
         main_frames = _frames(config.edited_contorl_frame_path_main, config.n_frames, config.image_size)
         obj_frames = [_frames(p, config.n_frames, config.image_size) for p in config.edited_contorl_frame_path]
         bg_frames = _frames(config.edited_contorl_frame_path_background, config.n_frames, config.image_size)
@@ -103,19 +153,34 @@ def main(template_config, configs_list, device, synthetic=False, dedup_sources=F
                   obj_ddim_latents_path=config.obj_ddim_latents_path,
                   obj_ddim_latents_idx_offset=config.obj_ddim_latents_idx_offset,
                   obj_random_noise_fusion=config.obj_random_noise_fusion, fusion_steps=config.fusion_step)
-        output_dir = os.path.join(config.output_dir, output_suffix(config))
-        os.makedirs(output_dir, exist_ok=True)
+        if variants is None:
+            output_dirs, configs = [os.path.join(config.output_dir, output_suffix(config))], [config]
+        else:  # K variants in one loop: per-variant prompt / negative prompt / seed / cfg / main image, everything else shared
+            output_dirs, configs = [variant_output_dir(c, k) for k, c in enumerate(variants)], variants
+            # (a variant that keeps the entry's main image passes the SAME object: one VAE draw, one vision-tower pass)
+            same_1st = lambda c: c.edited_first_frame_path == config.edited_first_frame_path
+            same_main = lambda c: c.edited_contorl_frame_path_main == config.edited_contorl_frame_path_main
+            kw.update(prompt=[c.editing_prompt for c in variants], negative_prompt=[c.editing_negative_prompt for c in variants],
+                      guidance_scale=[c.cfg for c in variants],
+                      generator=[torch.Generator().manual_seed(c.seed) for c in variants],
+                      main_first_image=[main_1st if same_1st(c) else first(c) for c in variants],
+                      main_image_list=[main_frames if same_main(c) else
+                                       _frames(c.edited_contorl_frame_path_main, c.n_frames, c.image_size) for c in variants])
+        for od in output_dirs:
+            os.makedirs(od, exist_ok=True)
         try:
-            video = pipe.sample_with_pnp_pipeline_with_edit_prompt_extraction_with_attn_injection(output_type=out_type, **kw).frames[0]
+            videos = pipe.sample_with_pnp_pipeline_with_edit_prompt_extraction_with_attn_injection(output_type=out_type, **kw).frames
         except NotImplementedError as e:  # no VAE decoder on this path: keep the composed latents
             logger.warning(f"composition decoded to latents only ({e})")
             lat = pipe.sample_with_pnp_pipeline_with_edit_prompt_extraction_with_attn_injection(output_type="latent", **kw).frames
-            torch.save(lat.cpu(), os.path.join(output_dir, "video_latents.pt"))
+            if variants is None:
+                torch.save(lat.cpu(), os.path.join(output_dirs[0], "video_latents.pt"))
+            else:
+                for k, od in enumerate(output_dirs):
+                    torch.save(lat[k:k + 1].cpu(), os.path.join(od, "video_latents.pt"))
             continue
-        video = [f.resize(tuple(config.image_size), resample=Image.LANCZOS) for f in video]
-        export_to_gif(video, os.path.join(output_dir, "video.gif"))
-        for i, f in enumerate(video):
-            f.save(os.path.join(output_dir, f"video_{i:05d}.png"))
+        for k, od in enumerate(output_dirs):
+            _write_video(videos[k], configs[k], od)
 
 
 if __name__ == "__main__":

@@ -306,6 +306,18 @@ int mvoc_pnp_blend_scatter_nchw(const mvoc_pnp_desc* d, void* stream);
  * (else -1 and an error text). */
 int mvoc_pnp_blend_scatter_tokens_mapped(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, void* stream);
 int mvoc_pnp_blend_scatter_nchw_mapped(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, void* stream);
+/* K variants over one set of sources (pipeline.py variants): nvar destination pairs share the source chunks, the
+ * batch is [s_0..s_{nsrc-1}, u_1..u_K, c_1..c_K] (ndst = 1: [s_0..s_{nsrc-1}, c_1..c_K]); nsrc / obj_chunk as above (the
+ * identity map {1..nobj} with nsrc = nobj + 1 is the positional source layout).  Every work item reads its nobj object vectors
+ * and mask values once; variant k blends them onto chunk 0 (base_chunk0 != 0: one blend, stored ndst*K times) or onto its own
+ * conditional chunk c_k, and stores to u_k and c_k (c_k only with ndst = 1).  The destination rows of variant k are
+ * bit-identical to the positional entry on that variant's own [bg, obj.., u_k, c_k] batch; nvar = 1 is the _mapped entry.
+ * Traffic per tensor: (distinct sources read + K bases when base_chunk0 == 0) + ndst*K chunks written.
+ * Requires 1 <= nvar <= 8 and a valid map (else -1 and an error text, nothing written). */
+int mvoc_pnp_blend_scatter_tokens_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
+                                           void* stream);
+int mvoc_pnp_blend_scatter_nchw_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
+                                         void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Loop glue on [B,4,F,h,w] fp16 latents, BIT-EXACT vs the reference's eager fp16 op chain.
@@ -321,6 +333,14 @@ int mvoc_ddim_step_f16(const void* x, const void* v_uncond, const void* v_cond, 
  * of contiguous [n] fp16 tensors: obj[j] at objs + j*n, mask[j] at masks + j*n */
 int mvoc_latent_fusion_f16(const void* latents, const void* bg, const void* objs, const void* masks, void* out,
                            int32_t nobj, int64_t n, double mix_ratio, int32_t obj_random_noise_fusion, void* stream);
+/* The two updates over K variants in one launch (1 <= nvar <= 8), bit-identical variant by variant to the entries above.
+ *   ddim_step:     x / v_uncond / v_cond / out are [nvar][n_per]; coef_dev is [nvar][5], element i uses row i / n_per
+ *   latent_fusion: latents / out are [nvar][n_per]; bg [n_per], objs / masks [nobj][n_per] are read by every variant */
+int mvoc_ddim_step_variants_f16(const void* x, const void* v_uncond, const void* v_cond, const float* coef_dev, void* out,
+                                int64_t n_per, int32_t nvar, void* stream);
+int mvoc_latent_fusion_variants_f16(const void* latents, const void* bg, const void* objs, const void* masks, void* out,
+                                    int32_t nobj, int64_t n_per, int32_t nvar, double mix_ratio,
+                                    int32_t obj_random_noise_fusion, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Stem / small ops (pipeline_i2vgen_xl.py:166-290, 351-357).

@@ -96,8 +96,12 @@ SIGNATURES = {
     "mvoc_pnp_blend_scatter_nchw": (i32, [C.POINTER(PnpDesc), vp]),
     "mvoc_pnp_blend_scatter_tokens_mapped": (i32, [C.POINTER(PnpDesc), i32, C.POINTER(i32), vp]),
     "mvoc_pnp_blend_scatter_nchw_mapped": (i32, [C.POINTER(PnpDesc), i32, C.POINTER(i32), vp]),
+    "mvoc_pnp_blend_scatter_tokens_variants": (i32, [C.POINTER(PnpDesc), i32, C.POINTER(i32), i32, vp]),
+    "mvoc_pnp_blend_scatter_nchw_variants": (i32, [C.POINTER(PnpDesc), i32, C.POINTER(i32), i32, vp]),
     "mvoc_ddim_step_f16": (i32, [vp, vp, vp, vp, vp, i64, vp]),
     "mvoc_latent_fusion_f16": (i32, [vp, vp, vp, vp, vp, i32, i64, f64, i32, vp]),
+    "mvoc_ddim_step_variants_f16": (i32, [vp, vp, vp, vp, vp, i64, i32, vp]),
+    "mvoc_latent_fusion_variants_f16": (i32, [vp, vp, vp, vp, vp, i32, i64, i32, f64, i32, vp]),
     "mvoc_timestep_embedding_f16": (i32, [vp, i32, i32, vp, vp]),
     "mvoc_act_f16": (i32, [vp, vp, i64, i32, vp]),
     "mvoc_add_f16": (i32, [vp, vp, vp, i64, vp]),

@@ -128,6 +128,128 @@ __global__ __launch_bounds__(256) void pnp_nchw_kernel(const PnpArgs p) {
   }
 }
 
+// ---- K variants over one set of source chunks ------------------------------------------------
+// Batch [s_0..s_{nsrc-1}, u_1..u_K, c_1..c_K] (ndst == 1: [s.., c_1..c_K]).  The object vectors and mask values of a work item
+// are read ONCE and stay in registers across the variant loop: NOBJ is a template parameter, so ov[] / m[] are indexed by
+// unrolled constants only (a run-time-indexed array would go to scratch, see PnpArgs.obj_map).  Per variant the arithmetic
+// is that of the kernels above: blend16 in object order on the variant's base.
+__device__ __forceinline__ int var_dst(const PnpArgs& p, int nvar, int d, int k) {  // d: 0 = first block of destinations
+  return p.nsrc + d * nvar + k;
+}
+
+template <int NOBJ>
+__global__ __launch_bounds__(256) void pnp_tokens_variants_kernel(const PnpArgs p, const int nvar) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= p.total) return;
+  half_t* x = p.x[blockIdx.y];
+  const int c8n = p.channels >> 3;
+  const int c8 = (int)(idx % c8n);
+  const long fp = idx / c8n;
+  const int hw = p.height * p.width;
+  const int f = (int)(fp / hw), px = (int)(fp % hw);
+  const int py = px / p.width, pxx = px - py * p.width;
+  const int my = nearest_src(py, p.sy, p.mask_h), mx = nearest_src(pxx, p.sx, p.mask_w);
+  const long off = (long)f * p.f_stride + (long)px * p.p_stride + c8 * 8;
+  half8_t ov[NOBJ];
+  float m[NOBJ];
+#pragma unroll
+  for (int j = 0; j < NOBJ; ++j) {
+    m[j] = (float)p.masks[(((long)j * p.frames + f) * p.mask_h + my) * p.mask_w + mx];
+    ov[j] = *reinterpret_cast<const half8_t*>(x + obj_chunk<true>(p, j) * p.chunk_stride + off);
+  }
+  half8_t o;
+  if (p.base_chunk0) {  // one blend for every variant
+    const half8_t bv = *reinterpret_cast<const half8_t*>(x + off);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float inj = (float)bv[e];
+#pragma unroll
+      for (int j = 0; j < NOBJ; ++j) inj = blend16(inj, (float)ov[j][e], m[j]);
+      o[e] = (half_t)inj;
+    }
+  }
+  for (int k = 0; k < nvar; ++k) {
+    half_t* cond = x + var_dst(p, nvar, p.ndst - 1, k) * p.chunk_stride + off;
+    if (!p.base_chunk0) {
+      const half8_t bv = *reinterpret_cast<const half8_t*>(cond);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        float inj = (float)bv[e];
+#pragma unroll
+        for (int j = 0; j < NOBJ; ++j) inj = blend16(inj, (float)ov[j][e], m[j]);
+        o[e] = (half_t)inj;
+      }
+    }
+    if (p.ndst == 2) *reinterpret_cast<half8_t*>(x + var_dst(p, nvar, 0, k) * p.chunk_stride + off) = o;
+    *reinterpret_cast<half8_t*>(cond) = o;
+  }
+}
+
+template <int VEC>
+__device__ __forceinline__ void ld_vec(half_t (&t)[VEC], const half_t* src) {
+  if constexpr (VEC == 8) *reinterpret_cast<half8_t*>(t) = *reinterpret_cast<const half8_t*>(src);
+  else t[0] = src[0];
+}
+
+template <int VEC>
+__device__ __forceinline__ void st_vec(half_t* dst, const half_t (&t)[VEC]) {
+  if constexpr (VEC == 8) *reinterpret_cast<half8_t*>(dst) = *reinterpret_cast<const half8_t*>(t);
+  else dst[0] = t[0];
+}
+
+template <int VEC, int NOBJ>
+__global__ __launch_bounds__(256) void pnp_nchw_variants_kernel(const PnpArgs p, const int nvar) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= p.total) return;
+  half_t* x = p.x[blockIdx.y];
+  const int hw = p.height * p.width;
+  const int pvn = hw / VEC;
+  const int pv = (int)(idx % pvn);
+  const long fc = idx / pvn;
+  const int f = (int)(fc / p.channels);
+  const long off = fc * hw + (long)pv * VEC;  // (f*C + c)*HW + p
+  const long chunk = (long)p.frames * p.channels * hw;
+  half_t ov[NOBJ][VEC];
+  float m[NOBJ][VEC];
+#pragma unroll
+  for (int j = 0; j < NOBJ; ++j) {
+    ld_vec<VEC>(ov[j], x + obj_chunk<true>(p, j) * chunk + off);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      const int px = pv * VEC + e;
+      const int py = px / p.width, pxx = px - py * p.width;
+      const int my = nearest_src(py, p.sy, p.mask_h), mx = nearest_src(pxx, p.sx, p.mask_w);
+      m[j][e] = (float)p.masks[(((long)j * p.frames + f) * p.mask_h + my) * p.mask_w + mx];
+    }
+  }
+  half_t tmp[VEC];
+  if (p.base_chunk0) {
+    ld_vec<VEC>(tmp, x + off);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      float inj = (float)tmp[e];
+#pragma unroll
+      for (int j = 0; j < NOBJ; ++j) inj = blend16(inj, (float)ov[j][e], m[j][e]);
+      tmp[e] = (half_t)inj;
+    }
+  }
+  for (int k = 0; k < nvar; ++k) {
+    half_t* cond = x + var_dst(p, nvar, p.ndst - 1, k) * chunk + off;
+    if (!p.base_chunk0) {
+      ld_vec<VEC>(tmp, cond);
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        float inj = (float)tmp[e];
+#pragma unroll
+        for (int j = 0; j < NOBJ; ++j) inj = blend16(inj, (float)ov[j][e], m[j][e]);
+        tmp[e] = (half_t)inj;
+      }
+    }
+    if (p.ndst == 2) st_vec<VEC>(x + var_dst(p, nvar, 0, k) * chunk + off, tmp);
+    st_vec<VEC>(cond, tmp);
+  }
+}
+
 int fill_args(const mvoc_pnp_desc* d, PnpArgs& a) {
   MVOC_REQUIRE(d && d->x && d->masks, -1, "pnp: null operand");
   MVOC_REQUIRE(d->nobj >= 1 && d->nobj <= 4, -2, "pnp: nobj %d not in [1,4]", d->nobj);
@@ -213,6 +335,47 @@ __global__ __launch_bounds__(256) void fusion_kernel(const half_t* __restrict__ 
   out[i] = (half_t)l;
 }
 
+// K variants: element i belongs to variant i / n_per and takes that variant's coefficient row; the arithmetic is
+// ddim_step_kernel's, operation for operation
+__global__ __launch_bounds__(256) void ddim_step_variants_kernel(const half_t* __restrict__ x, const half_t* __restrict__ vu,
+                                                                 const half_t* __restrict__ vc, const float* __restrict__ coef,
+                                                                 half_t* __restrict__ out, long n_per, long n) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float* cf = coef + 5 * (i / n_per);
+  const float sa = cf[0], sb = cf[1], sp = cf[2], sq = cf[3], g = cf[4];
+  const float xs = (float)x[i];
+  float v = (float)vc[i];
+  if (vu) {
+    const float u = (float)vu[i];
+    v = r16(u + smul16(g, r16(v - u)));
+  }
+  const float x0 = r16(smul16(sa, xs) - smul16(sb, v));
+  const float eps = r16(smul16(sa, v) + smul16(sb, xs));
+  const float dir = smul16(sq, eps);
+  out[i] = (half_t)(smul16(sp, x0) + dir);
+}
+
+// K variants: latents / out are [nvar][n_per]; background, objects and masks are [n_per] and read by every variant
+__global__ __launch_bounds__(256) void fusion_variants_kernel(const half_t* __restrict__ lat, const half_t* __restrict__ bg,
+                                                              const half_t* __restrict__ objs, const half_t* __restrict__ masks,
+                                                              half_t* __restrict__ out, int nobj, long n_per, long n, float mix,
+                                                              float omix, int rnf) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const long r = i % n_per;
+  float l = r16(smul16(mix, (float)lat[i]) + smul16(omix, (float)bg[r]));
+  for (int j = 0; j < nobj; ++j) {
+    const float m = (float)masks[(long)j * n_per + r];
+    const float inv_obj = r16((float)objs[(long)j * n_per + r] * m);
+    const float background = r16(l * r16(1.0f - m));
+    float fusion = inv_obj;
+    if (rnf) fusion = r16(smul16(mix, r16(l * m)) + smul16(omix, inv_obj));
+    l = r16(background + fusion);
+  }
+  out[i] = (half_t)l;
+}
+
 }  // namespace
 
 namespace {
@@ -251,7 +414,100 @@ int launch_nchw(const mvoc_pnp_desc* d, PnpArgs& a, int nread, void* stream) {
   return mvoc_check_launch("pnp_nchw_kernel");
 }
 
+// variants: nsrc_read distinct source chunks read (+ K bases unless the base is chunk 0), ndst * K chunks written
+int fill_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar, PnpArgs& a, double& chunks) {
+  MVOC_REQUIRE(nvar >= 1 && nvar <= 8, -1, "pnp variants: nvar %d not in [1, 8]", nvar);
+  int nread = 0;
+  if (int rc = fill_args(d, a)) return rc;
+  if (int rc = fill_map(d, nsrc, obj_chunk, a, nread)) return rc;
+  chunks = (d->base_chunk0 ? nread : nread - 1 + nvar) + (double)a.ndst * nvar;
+  return 0;
+}
+
+template <int NOBJ>
+void launch_nchw_variants_n(bool vec, dim3 grid, hipStream_t s, const PnpArgs& a, int nvar) {
+  if (vec)
+    hipLaunchKernelGGL((pnp_nchw_variants_kernel<8, NOBJ>), grid, dim3(256), 0, s, a, nvar);
+  else
+    hipLaunchKernelGGL((pnp_nchw_variants_kernel<1, NOBJ>), grid, dim3(256), 0, s, a, nvar);
+}
+
 }  // namespace
+
+extern "C" int mvoc_pnp_blend_scatter_tokens_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
+                                                      int32_t nvar, void* stream) {
+  PnpArgs a;
+  double chunks = 0;
+  if (int rc = fill_variants(d, nsrc, obj_chunk, nvar, a, chunks)) return rc;
+  MVOC_REQUIRE(d->channels % 8 == 0 && d->chunk_stride % 8 == 0 && d->f_stride % 8 == 0 && d->p_stride % 8 == 0, -2,
+               "pnp tokens: channels/strides must be multiples of 8");
+  a.total = (long)d->frames * d->height * d->width * (d->channels / 8);
+  const long nblk = (a.total + 255) / 256;
+  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "pnp tokens: grid too large");
+  const int ntens = d->x2 ? 2 : 1;
+  hipStream_t s = (hipStream_t)stream;
+  const double elems = (double)d->frames * d->height * d->width * d->channels;
+  MvocProfScope prof(MVOC_FAM_PNP, s, ntens * (elems * 2.0 * chunks + 2.0 * d->nobj * d->frames * d->height * d->width));
+  const dim3 grid((unsigned)nblk, ntens);
+  switch (d->nobj) {
+    case 1: hipLaunchKernelGGL(pnp_tokens_variants_kernel<1>, grid, dim3(256), 0, s, a, (int)nvar); break;
+    case 2: hipLaunchKernelGGL(pnp_tokens_variants_kernel<2>, grid, dim3(256), 0, s, a, (int)nvar); break;
+    case 3: hipLaunchKernelGGL(pnp_tokens_variants_kernel<3>, grid, dim3(256), 0, s, a, (int)nvar); break;
+    default: hipLaunchKernelGGL(pnp_tokens_variants_kernel<4>, grid, dim3(256), 0, s, a, (int)nvar); break;
+  }
+  return mvoc_check_launch("pnp_tokens_variants_kernel");
+}
+
+extern "C" int mvoc_pnp_blend_scatter_nchw_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
+                                                    int32_t nvar, void* stream) {
+  PnpArgs a;
+  double chunks = 0;
+  if (int rc = fill_variants(d, nsrc, obj_chunk, nvar, a, chunks)) return rc;
+  const long hw = (long)d->height * d->width;
+  const bool vec = hw % 8 == 0;
+  a.total = (long)d->frames * d->channels * (vec ? hw / 8 : hw);
+  const long nblk = (a.total + 255) / 256;
+  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "pnp nchw: grid too large");
+  const int ntens = d->x2 ? 2 : 1;
+  hipStream_t s = (hipStream_t)stream;
+  const double elems = (double)d->frames * hw * d->channels;
+  MvocProfScope prof(MVOC_FAM_PNP, s, ntens * (elems * 2.0 * chunks + 2.0 * d->nobj * d->frames * hw));
+  const dim3 grid((unsigned)nblk, ntens);
+  switch (d->nobj) {
+    case 1: launch_nchw_variants_n<1>(vec, grid, s, a, nvar); break;
+    case 2: launch_nchw_variants_n<2>(vec, grid, s, a, nvar); break;
+    case 3: launch_nchw_variants_n<3>(vec, grid, s, a, nvar); break;
+    default: launch_nchw_variants_n<4>(vec, grid, s, a, nvar); break;
+  }
+  return mvoc_check_launch("pnp_nchw_variants_kernel");
+}
+
+extern "C" int mvoc_ddim_step_variants_f16(const void* x, const void* v_uncond, const void* v_cond, const float* coef_dev,
+                                           void* out, int64_t n_per, int32_t nvar, void* stream) {
+  MVOC_REQUIRE(x && v_cond && coef_dev && out && n_per > 0, -1, "ddim_step_variants: null operand / empty");
+  MVOC_REQUIRE(nvar >= 1 && nvar <= 8, -1, "ddim_step_variants: nvar %d not in [1, 8]", nvar);
+  hipStream_t s = (hipStream_t)stream;
+  const long n = (long)n_per * nvar;
+  MvocProfScope prof(MVOC_FAM_MISC, s, 2.0 * n * (v_uncond ? 4 : 3));
+  hipLaunchKernelGGL(ddim_step_variants_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const half_t*)x,
+                     (const half_t*)v_uncond, (const half_t*)v_cond, coef_dev, (half_t*)out, (long)n_per, n);
+  return mvoc_check_launch("ddim_step_variants_kernel");
+}
+
+extern "C" int mvoc_latent_fusion_variants_f16(const void* latents, const void* bg, const void* objs, const void* masks,
+                                               void* out, int32_t nobj, int64_t n_per, int32_t nvar, double mix_ratio,
+                                               int32_t obj_random_noise_fusion, void* stream) {
+  MVOC_REQUIRE(latents && bg && objs && masks && out && n_per > 0 && nobj >= 0, -1, "latent_fusion_variants: null operand / empty");
+  MVOC_REQUIRE(nvar >= 1 && nvar <= 8, -1, "latent_fusion_variants: nvar %d not in [1, 8]", nvar);
+  hipStream_t s = (hipStream_t)stream;
+  const long n = (long)n_per * nvar;
+  MvocProfScope prof(MVOC_FAM_MISC, s, 2.0 * n * 2 + 2.0 * n_per * (1 + 2 * nobj));
+  const float mix = (float)mix_ratio, omix = (float)(1.0 - mix_ratio);  // as mvoc_latent_fusion_f16 forms them
+  hipLaunchKernelGGL(fusion_variants_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const half_t*)latents,
+                     (const half_t*)bg, (const half_t*)objs, (const half_t*)masks, (half_t*)out, nobj, (long)n_per, n, mix, omix,
+                     obj_random_noise_fusion);
+  return mvoc_check_launch("fusion_variants_kernel");
+}
 
 extern "C" int mvoc_pnp_blend_scatter_tokens(const mvoc_pnp_desc* d, void* stream) {
   PnpArgs a;

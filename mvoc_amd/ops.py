@@ -514,13 +514,36 @@ def _src_map_args(src_map, nobj):
     return int(nsrc), (C.c_int32 * nobj)(*[int(c) for c in chunks])
 
 
+def _variant_map(src_map, nobj):
+    """the ``_variants`` entries always take a map: the positional sources [bg, obj_1..obj_n] are the identity map"""
+    return _src_map_args(src_map if src_map is not None else (nobj + 1, tuple(range(1, nobj + 1))), nobj)
+
+
+def _check_variants(x, x2, nvar, need, what):
+    """the variants kernels address chunk nsrc + ndst*nvar - 1 of each tensor: refuse a buffer that does not reach it"""
+    if not 1 <= int(nvar) <= 8:
+        raise RuntimeError(f"{what}: variants {nvar} not in [1, 8]")
+    for t in (x, x2):
+        if t is not None and t.storage_offset() + need > t.untyped_storage().nbytes() // t.element_size():
+            raise RuntimeError(f"{what}: the tensor's storage ends before the last destination chunk "
+                               f"(needs {need} elements from its first)")
+
+
 def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride, f_stride, p_stride, x2=None,
-                     base_chunk0=False, ndst=2, src_map=None):
+                     base_chunk0=False, ndst=2, src_map=None, nvar=1):
     """In-place masked blend + scatter on channel-contiguous data (see include/mvoc_hip.h).  ``ndst``: trailing
     destination chunks (2 = [uncond, cond], 1 = [cond] with CFG off).  ``src_map`` = (nsrc, obj_chunks): the batch holds
-    nsrc de-duplicated source chunks, object j reads chunk obj_chunks[j] (None: [bg, obj_1..obj_n], the unmapped entry)."""
+    nsrc de-duplicated source chunks, object j reads chunk obj_chunks[j] (None: [bg, obj_1..obj_n], the unmapped entry).
+    ``nvar`` = K > 1: K variants share the sources, the batch is [s.., u_1..u_K, c_1..c_K] ([s.., c_1..c_K] with ndst 1)."""
     d = _pnp_desc(x, x2, masks, chunk_stride, f_stride, p_stride, frames, height, width, channels, base_chunk0, ndst)
-    if src_map is None:
+    if nvar != 1:
+        nsrc, chunks = _variant_map(src_map, d.nobj)
+        last = (nsrc + (int(ndst) or 2) * int(nvar) - 1) * chunk_stride
+        _check_variants(x, x2, nvar, last + (frames - 1) * f_stride + (height * width - 1) * p_stride + channels,
+                        "pnp_blend_tokens")
+        check(lib.mvoc_pnp_blend_scatter_tokens_variants(C.byref(d), nsrc, chunks, int(nvar), _stream()),
+              "pnp_blend_scatter_tokens_variants")
+    elif src_map is None:
         check(lib.mvoc_pnp_blend_scatter_tokens(C.byref(d), _stream()), "pnp_blend_scatter_tokens")
     else:
         nsrc, chunks = _src_map_args(src_map, d.nobj)
@@ -528,13 +551,18 @@ def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride,
     return x
 
 
-def pnp_blend_nchw(x, masks, *, frames, x2=None, base_chunk0=True, ndst=2, src_map=None):
+def pnp_blend_nchw(x, masks, *, frames, x2=None, base_chunk0=True, ndst=2, src_map=None, nvar=1):
     """In-place on x [(nobj+1+ndst)*F, C, H, W] (reference feature-map layout); with ``src_map`` = (nsrc, obj_chunks)
-    x is [(nsrc+ndst)*F, C, H, W] (see ``pnp_blend_tokens``)."""
+    x is [(nsrc+ndst)*F, C, H, W], with ``nvar`` = K > 1 [(nsrc+ndst*K)*F, C, H, W] (see ``pnp_blend_tokens``)."""
     if x.dim() != 4 or not x.is_contiguous():
         raise RuntimeError("pnp_blend_nchw: x must be contiguous [N, C, H, W]")
     d = _pnp_desc(x, x2, masks, 0, 0, 0, frames, x.shape[2], x.shape[3], x.shape[1], base_chunk0, ndst)
-    if src_map is None:
+    if nvar != 1:
+        nsrc, chunks = _variant_map(src_map, d.nobj)
+        _check_variants(x, x2, nvar, (nsrc + (int(ndst) or 2) * int(nvar)) * frames * x[0].numel(), "pnp_blend_nchw")
+        check(lib.mvoc_pnp_blend_scatter_nchw_variants(C.byref(d), nsrc, chunks, int(nvar), _stream()),
+              "pnp_blend_scatter_nchw_variants")
+    elif src_map is None:
         check(lib.mvoc_pnp_blend_scatter_nchw(C.byref(d), _stream()), "pnp_blend_scatter_nchw")
     else:
         nsrc, chunks = _src_map_args(src_map, d.nobj)
@@ -543,23 +571,43 @@ def pnp_blend_nchw(x, masks, *, frames, x2=None, base_chunk0=True, ndst=2, src_m
 
 
 def ddim_step(x, v_cond, coef_dev, v_uncond=None, out=None):
-    """coef_dev: fp32 device tensor {sqrt(a_t), sqrt(1-a_t), sqrt(a_prev), sqrt(1-a_prev), guidance_scale}."""
+    """coef_dev: fp32 device tensor {sqrt(a_t), sqrt(1-a_t), sqrt(a_prev), sqrt(1-a_prev), guidance_scale}; a [K, 5] tensor
+    with K > 1 updates K variants in one launch: x, v_cond, v_uncond, out are then [K, ...] and variant k takes row k."""
     _chk(x, "x"), _chk(v_cond, "v_cond"), _chk(v_uncond, "v_uncond"), _chk(coef_dev, "coef", torch.float32)
     if out is None:
         out = torch.empty_like(x)
     for t in (x, v_cond, v_uncond, out):
         if t is not None and not t.is_contiguous():
             raise RuntimeError("ddim_step: tensors must be contiguous")
+    if coef_dev.dim() == 2 and coef_dev.shape[0] > 1:
+        nvar = coef_dev.shape[0]
+        if not coef_dev.is_contiguous() or coef_dev.shape[1] != 5 or x.shape[0] != nvar or any(
+                t is not None and t.numel() != x.numel() for t in (v_cond, v_uncond, out)):
+            raise RuntimeError(f"ddim_step: {nvar} coefficient rows need contiguous [{nvar}, 5] and [{nvar}, ...] tensors of one size")
+        check(lib.mvoc_ddim_step_variants_f16(x.data_ptr(), _ptr(v_uncond), v_cond.data_ptr(), coef_dev.data_ptr(),
+                                              out.data_ptr(), x.numel() // nvar, nvar, _stream()), "ddim_step_variants")
+        return out
     check(lib.mvoc_ddim_step_f16(x.data_ptr(), _ptr(v_uncond), v_cond.data_ptr(), coef_dev.data_ptr(), out.data_ptr(),
                                  x.numel(), _stream()), "ddim_step")
     return out
 
 
-def latent_fusion(latents, bg, objs, masks, mix_ratio, obj_random_noise_fusion=False, out=None):
-    """objs / masks: contiguous [nobj, *latents.shape] fp16."""
+def latent_fusion(latents, bg, objs, masks, mix_ratio, obj_random_noise_fusion=False, out=None, nvar=1):
+    """objs / masks: contiguous [nobj, *latents.shape] fp16.  ``nvar`` = K > 1: latents / out are [K, ...] (K variants), bg is
+    one variant's size and objs / masks are [nobj, *bg.shape], read by every variant."""
     _chk(latents, "latents"), _chk(bg, "bg"), _chk(objs, "objs"), _chk(masks, "masks")
     if out is None:
         out = torch.empty_like(latents)
+    if nvar != 1:
+        n = bg.numel()
+        if not 1 <= nvar <= 8 or latents.numel() != n * nvar or out.numel() != n * nvar or objs.numel() != masks.numel() \
+                or objs.numel() % n or not all(t.is_contiguous() for t in (latents, bg, objs, masks, out)):
+            raise RuntimeError(f"latent_fusion: {nvar} variants need contiguous latents/out [{nvar}, ...bg.shape] and objs/masks "
+                               "[nobj, ...bg.shape]")
+        check(lib.mvoc_latent_fusion_variants_f16(latents.data_ptr(), bg.data_ptr(), objs.data_ptr(), masks.data_ptr(),
+                                                  out.data_ptr(), objs.numel() // n, n, int(nvar), float(mix_ratio),
+                                                  int(obj_random_noise_fusion), _stream()), "latent_fusion_variants")
+        return out
     n = latents.numel()
     if objs.numel() != masks.numel() or objs.numel() % n:
         raise RuntimeError("latent_fusion: objs/masks must be [nobj, ...latents.shape]")

@@ -156,6 +156,50 @@ def source_rows(smap, n_obj):
     return [0] + [1 + chunks.index(c) for c in range(1, nsrc)]
 
 
+MAX_VARIANTS = 8
+
+
+def variant_layout(n_obj, nvar=1, do_cfg=True, smap=None):
+    """Chunk indices of a composition batch of ``nvar`` = K variants over one set of sources:
+    [s_0..s_{nsrc-1}, u_1..u_K, c_1..c_K] with guidance, [s_0..s_{nsrc-1}, c_1..c_K] without.  ``smap``: the source map of
+    ``plan_source_map`` (None: every role its own chunk).  Blocks rather than interleaved pairs: the paired attention serves
+    the K pairs in one launch (the c block sits at a constant offset behind the u block) and the u / c noise predictions are
+    each contiguous for the DDIM update.  K = 1 is the positional layout.
+    -> dict(nsrc, nb, src = chunk of every source role (background first), obj_chunks, u = [K] or None, c = [K], ndst)"""
+    if not 1 <= int(nvar) <= MAX_VARIANTS:
+        raise ValueError(f"variants: {nvar} not in [1, {MAX_VARIANTS}]")
+    if not 1 <= n_obj <= 4:
+        raise ValueError(f"variants: {n_obj} objects not in [1, 4]")
+    if smap is None:
+        nsrc, chunks = n_obj + 1, tuple(range(1, n_obj + 1))
+    else:
+        nsrc, chunks = int(smap[0]), tuple(int(c) for c in smap[1])
+        if len(chunks) != n_obj or not 1 <= nsrc <= n_obj + 1 or any(not 0 <= c < nsrc for c in chunks):
+            raise ValueError(f"variants: source map {smap} does not fit {n_obj} objects")
+    ndst = 2 if do_cfg else 1
+    u = [nsrc + k for k in range(nvar)] if do_cfg else None
+    c = [nsrc + (ndst - 1) * nvar + k for k in range(nvar)]
+    return dict(nsrc=nsrc, nb=nsrc + ndst * nvar, src=[0] + list(chunks), obj_chunks=chunks, u=u, c=c, ndst=ndst)
+
+
+def crosses_gemm_offset_line(nb, frames, h, w, width0):
+    """the eight-phase GEMM tiles address their operands with 32-bit byte offsets (gemm.hip g8_ok): the widest level-0 tensor
+    of a forward, the feed-forward's [nb * F * h * w, 4 * width0] fp16, must stay under 2 GB for them to be chosen"""
+    return nb * frames * h * w * 4 * width0 * 2 >= 2 ** 31
+
+
+def _per_variant(value, n_prompts, m, what, is_scalar):
+    """a scalar (shared by every variant) or a list -- one entry per prompt (each repeated m times) or one per variant"""
+    if is_scalar(value):
+        return [value] * (n_prompts * m)
+    value = list(value)
+    if len(value) == n_prompts * m:
+        return value
+    if len(value) == n_prompts:
+        return [v for v in value for _ in range(m)]
+    raise ValueError(f"{what}: {len(value)} entries for {n_prompts} prompts x {m} videos per prompt")
+
+
 class GraphedStep:
     """Capture one loop iteration (a python callable working on static device buffers) into a hipGraph."""
 
@@ -515,32 +559,45 @@ class I2VGenXLPipeline:
         return tensor2vid(self.conditioner.decode(latents), output_type)
 
     # ---- composition --------------------------------------------------------------------------------------
-    def make_composition_state(self, latents, cond, masks, guidance_scale, dedup_sources=None):
+    def make_composition_state(self, latents, cond, masks, guidance_scale, dedup_sources=None, variants=1):
         """static buffers + the captured iteration variants of the composition loop.
         cond: dict(encoder_hidden_states [n,77,D], image_embeddings [n,F,D], image_latents_first, image_latents, fps).
         The state keeps its OWN copy of ``cond``: the hoisted conditioning (``prepare_conditioning``) and the shared-CFG-prefix
         decision below are taken once from these values, so a caller that later rewrites its tensors in place cannot make the
         captured iterations disagree with them -- new conditioning = a new state.
         ``dedup_sources`` (None: ``self.dedup_sources``): classify the source roles once (``source_classes``); every step then
-        runs the batch its source map (``plan_source_map``) lays out, each map with its own buffers, built on first use."""
+        runs the batch its source map (``plan_source_map``) lays out, each map with its own buffers, built on first use.
+        ``variants`` = K > 1: ``latents`` is [K, 4, F, h, w], ``cond`` rows follow ``variant_layout`` ([bg, obj.., u_1..u_K,
+        c_1..c_K]), ``guidance_scale`` is a float or K floats (all > 1 or none), a step's coefficient rows are [K, 5]."""
         cond = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in cond.items()}
         n_obj = len(masks)
-        do_cfg = guidance_scale > 1  # off: batch [bg, objs.., cond], one destination chunk for the injections (SURVEY 8f-4)
-        nb = n_obj + (3 if do_cfg else 2)
+        nvar = int(variants)
+        scales = [float(g) for g in guidance_scale] if isinstance(guidance_scale, (list, tuple)) else [float(guidance_scale)]
+        do_cfg = scales[0] > 1  # off: batch [bg, objs.., cond], one destination chunk for the injections (SURVEY 8f-4)
+        if any((g > 1) != do_cfg for g in scales):
+            raise ValueError("variants: guidance is on (scale > 1) for all variants of a call or off for all")
+        lay = variant_layout(n_obj, nvar, do_cfg)
+        nb = lay["nb"]
+        if latents.shape[0] != nvar:
+            raise ValueError(f"composition state: {nvar} variants need latents [{nvar}, 4, F, h, w], got {tuple(latents.shape)}")
+        if nvar > 1 and self.unet.shard is not None:
+            raise RuntimeError("variants > 1 do not combine with the frame shard: run one composition per call")
         dev = self.device
         dedup = self.dedup_sources if dedup_sources is None else bool(dedup_sources)
         st = {"latents": latents.clone(), "inp": torch.empty((nb,) + tuple(latents.shape[1:]), dtype=H16, device=dev),
-              "t": torch.zeros(1, dtype=torch.float32, device=dev), "coef": torch.zeros(5, dtype=torch.float32, device=dev),
-              "masks": masks, "variants": {}, "cond": cond, "n_obj": n_obj,
+              "t": torch.zeros(1, dtype=torch.float32, device=dev),
+              "coef": torch.zeros(5 if nvar == 1 else (nvar, 5), dtype=torch.float32, device=dev),
+              "masks": masks, "variants": {}, "cond": cond, "n_obj": n_obj, "nvar": nvar,
               "fusion_masks": torch.stack([m[0].to(dev, H16) for m in masks]).contiguous(),
-              "fusion_objs": torch.empty((n_obj,) + tuple(latents.shape), dtype=H16, device=dev), "maps": {}}
+              "fusion_objs": torch.empty((n_obj, 1) + tuple(latents.shape[1:]), dtype=H16, device=dev), "maps": {}}
         st["build_map"] = lambda smap: self._composition_batch(st, smap, do_cfg)
         st["maps"][None] = st["build_map"](None)
 
         # classifier-free guidance: the unconditional and the conditional chunk receive the same latent (below); when their image
         # latents and fps are equal too -- the reference builds both from the main image, pipeline_i2vgen_xl.py:1676-1690 -- they
         # differ only in what the cross-attentions see, and the UNet shares their common prefix (unet.shared_prefix_chunks)
-        share = bool(self.share_cfg_prefix and do_cfg and
+        # (K variants: off -- the prefix would save the network up to the first cross-attention only, DESIGN.md 6i)
+        share = bool(self.share_cfg_prefix and do_cfg and nvar == 1 and
                      all(torch.equal(cond[k][nb - 2], cond[k][nb - 1]) for k in ("image_latents_first", "image_latents", "fps")))
         st["share_cfg_prefix"] = share
         # (a frame-sharded clip runs the full layout: no de-duplication)
@@ -552,11 +609,11 @@ class I2VGenXLPipeline:
     def _composition_batch(self, st, smap, do_cfg):
         """the UNet batch of one source map (None: the positional [bg, obj_1..obj_n, (uncond,) cond]): its input buffer, its
         rows of the conditioning, the hoisted conditioning and the iteration body"""
-        n_obj, cond = st["n_obj"], st["cond"]
+        n_obj, cond, nvar = st["n_obj"], st["cond"], st["nvar"]
         if smap is None:
             inp, mcond = st["inp"], cond
         else:
-            nb_full = n_obj + (3 if do_cfg else 2)
+            nb_full = n_obj + 1 + (2 if do_cfg else 1) * nvar
             rows = torch.tensor(source_rows(smap, n_obj) + list(range(n_obj + 1, nb_full)), device=self.device)
             mcond = {k: v.index_select(0, rows.to(v.device)).contiguous() for k, v in cond.items()}
             inp = torch.empty((len(rows),) + tuple(st["latents"].shape[1:]), dtype=H16, device=self.device)
@@ -566,22 +623,23 @@ class I2VGenXLPipeline:
                                                   mcond["encoder_hidden_states"], False)
 
         def body():
-            x = st["latents"]
+            x = st["latents"]  # [K, 4, F, h, w]: every variant's latent into its u_k and c_k chunk
             if do_cfg:
-                inp[nb - 2].copy_(x[0])
-            inp[nb - 1].copy_(x[0])
+                inp[nb - 2 * nvar:nb - nvar].copy_(x)
+            inp[nb - nvar:].copy_(x)
             u = self.unet
             saved, u.prune_source_tail = u.prune_source_tail, bool(self.prune_source_tail)  # this loop reads the destination chunks only
             saved_sp, u.shared_prefix_chunks = u.shared_prefix_chunks, (2 if st["share_cfg_prefix"] else 0)
             saved_sc, u.source_chunks = u.source_chunks, smap
+            saved_nv, u.variants = u.variants, nvar
             try:
                 noise = u.forward_ext(inp, st["t"], mcond["fps"], mcond["image_latents_first"], mcond["image_latents"],
                                       mcond["image_embeddings"], mcond["encoder_hidden_states"], multi_frame_guidance=False,
                                       conditioning=prepared)[0]
             finally:
-                u.prune_source_tail, u.shared_prefix_chunks, u.source_chunks = saved, saved_sp, saved_sc
-            ops.ddim_step(x, noise[nb - 1:nb].contiguous(), st["coef"],
-                          v_uncond=noise[nb - 2:nb - 1].contiguous() if do_cfg else None, out=x)
+                u.prune_source_tail, u.shared_prefix_chunks, u.source_chunks, u.variants = saved, saved_sp, saved_sc, saved_nv
+            ops.ddim_step(x, noise[nb - nvar:nb].contiguous(), st["coef"],
+                          v_uncond=noise[nb - 2 * nvar:nb - nvar].contiguous() if do_cfg else None, out=x)
 
         return {"inp": inp, "cond": mcond, "prepared": prepared, "body": body, "nb": nb}
 
@@ -593,7 +651,8 @@ class I2VGenXLPipeline:
             mix, rnf, fobjs = fuse
             for j, o in enumerate(fobjs):
                 st["fusion_objs"][j].copy_(o)
-            ops.latent_fusion(st["latents"], bg_latents, st["fusion_objs"], st["fusion_masks"], mix, rnf, out=st["latents"])
+            ops.latent_fusion(st["latents"], bg_latents, st["fusion_objs"], st["fusion_masks"], mix, rnf, out=st["latents"],
+                              nvar=st["nvar"])
             obj_latents = fobjs
         smap = plan_source_map(st.get("classes"), [bg_latents] + list(obj_latents))
         b = st["maps"].get(smap)
@@ -612,7 +671,7 @@ class I2VGenXLPipeline:
         # device copies of the masks and the batch's source map: all are part of the variant key
         u = self.unet
         vkey = (u.injection_flags(), u.mask_key(st["masks"]), bool(u.pair_destinations), bool(u.prune_dead_chunks),
-                bool(self.prune_source_tail), bool(st.get("share_cfg_prefix")), smap)
+                bool(self.prune_source_tail), bool(st.get("share_cfg_prefix")), smap, st["nvar"])
         g = st["variants"].get(vkey)
         if g is None:
             g = st["variants"][vkey] = GraphedStep(b["body"], preserve=(st["latents"],))
@@ -629,8 +688,46 @@ class I2VGenXLPipeline:
             obj_ddim_latents_idx_offset=None, obj_random_noise_fusion=False, random_noise_ratio=0.0,
             bg_inv_latents_path=None, obj_ddim_latents_path=None, obj_masks_tensors=None):
         """PnP composition sampling.  ``obj_mask``: list of mask paths (preprocessed by ``mvoc_amd.utils.mask_preprocess``)
-        or pass ``obj_masks_tensors`` = list of (float [1,4,F,h,w], bool [1,4,F,h,w]) directly."""
+        or pass ``obj_masks_tensors`` = list of (float [1,4,F,h,w], bool [1,4,F,h,w]) directly.
+
+        K variants over one set of sources: ``prompt`` / ``negative_prompt`` may be lists, ``generator`` a list
+        (one per video; a single generator is drawn K times), ``latents`` [K, 4, F, h, w], ``guidance_scale`` a float or a
+        list, ``main_first_image`` a list of images and ``main_image_list`` a list of frame lists; ``num_videos_per_prompt`` =
+        m repeats each prompt m times (K = len(prompt) * m).  The sources, masks, schedules and fusion settings are shared; the
+        call returns K videos (``frames[k]``).  Scalars mean what they mean in a single composition."""
         from .utils import mask_preprocess
+        # ---- the variants of this call (one with scalar arguments: the batch, kernels and launches of a single composition)
+        m_rep = int(num_videos_per_prompt)
+        if m_rep < 1:
+            raise ValueError(f"num_videos_per_prompt = {num_videos_per_prompt}")
+        if prompt_embeds is not None:
+            n_prompts = prompt_embeds.shape[0]
+            prompts = [None] * (n_prompts * m_rep)
+        else:
+            plist = list(prompt) if isinstance(prompt, (list, tuple)) else [prompt]
+            n_prompts = len(plist)
+            prompts = [p for p in plist for _ in range(m_rep)]
+        nvar = len(prompts)
+        if not 1 <= nvar <= MAX_VARIANTS:
+            raise ValueError(f"{nvar} variants (prompts x num_videos_per_prompt): 1 to {MAX_VARIANTS} share one set of sources")
+        scalar = lambda v: not isinstance(v, (list, tuple))
+        negs = _per_variant(negative_prompt, n_prompts, m_rep, "negative_prompt", scalar)
+        scales = [float(g) for g in _per_variant(guidance_scale, n_prompts, m_rep, "guidance_scale", scalar)]
+        # (per-variant images come as a LIST of images / of frame lists; anything else is one image / one frame list for all)
+        mains_first = _per_variant(main_first_image, n_prompts, m_rep, "main_first_image", lambda v: not isinstance(v, list))
+        mains_list = _per_variant(main_image_list, n_prompts, m_rep, "main_image_list",
+                                  lambda v: not (isinstance(v, list) and len(v) and isinstance(v[0], list)))
+        if isinstance(generator, (list, tuple)):
+            if len(generator) != nvar:
+                raise ValueError(f"generator: {len(generator)} generators for {nvar} videos")
+            gens = list(generator)
+        else:
+            gens = [generator] * nvar  # one generator: drawn once per video, variant 0 first
+        if latents is not None and latents.shape[0] != nvar:
+            raise ValueError(f"latents: batch {latents.shape[0]} for {nvar} videos")
+        guidance_scale = scales[0]
+        if any((g > 1) != (guidance_scale > 1) for g in scales):
+            raise ValueError("guidance_scale: guidance is on (> 1) for all variants of a call or off for all")
         self._guidance_scale = guidance_scale
         # guidance_scale <= 1: classifier-free guidance off.  The reference's hooks hard-code the batch of 5
         # (pnp_utils.py:592,747,784,972,1061,1115: `// 5`) and cannot run this; here the batch is [bg, objs.., cond], the
@@ -657,16 +754,21 @@ class I2VGenXLPipeline:
             # (a conditioner without the batched entry -- the documented interface is encode_image -- is called per frame)
             return c.encode_images(frames) if hasattr(c, "encode_images") else torch.cat([c.encode_image(f) for f in frames])
         # conditioning, assembled in the reference's batch order [bg, obj_1.., uncond, cond] (:1387, 1476, 1498, 1540)
-        pe, ne = (prompt_embeds, negative_prompt_embeds) if prompt_embeds is not None else c.encode_prompt(prompt, negative_prompt)
-        inv_pe, _ = c.encode_prompt(ddim_inv_prompt, negative_prompt)
-        ehs = torch.cat([inv_pe.repeat(n_obj + 1, 1, 1)] + ([ne] if do_cfg else []) + [pe])
+        # (variants: the sources and variant 0 draw in the order of a single composition, the other variants after)
+        if prompt_embeds is not None:
+            pes = list(prompt_embeds.repeat_interleave(m_rep, 0).split(1))
+            nes = list(negative_prompt_embeds.repeat_interleave(m_rep, 0).split(1)) if negative_prompt_embeds is not None else [None] * nvar
+            pe, ne = pes[0], nes[0]
+        else:
+            pe, ne = c.encode_prompt(prompts[0], negs[0])
+            pes, nes = [pe], [ne]
+        inv_pe, _ = c.encode_prompt(ddim_inv_prompt, negs[0])
+        main_first_image, main_image_list = mains_first[0], mains_list[0]
         main_lat = image_latents(main_first_image)
         bg_lat = image_latents(background_first_image)
         obj_first = [image_latents(im) for im in objs_first_image]
-        first_all = torch.cat([bg_lat] + obj_first + [main_lat] * (2 if do_cfg else 1))
         obj_lat = [image_latents(frames[0]) for frames in objs_image_list]
         bg_lat2 = image_latents(background_image_list[0])
-        lat_all = torch.cat([bg_lat2] + obj_lat + [main_lat] * (2 if do_cfg else 1))
 
         # every conditioning frame of the job (background, objects, main: 4 x 16 in the demo) through the vision tower at once
         lists = [background_image_list] + list(objs_image_list) + [main_image_list]
@@ -686,8 +788,21 @@ class I2VGenXLPipeline:
             embs.append(flat[o:o + len(fr)].transpose(0, 1))  # [1, F, 1024]
             o += len(fr)
         main_emb = embs[-1]
-        emb_all = torch.cat(embs[:-1] + ([torch.zeros_like(main_emb)] if do_cfg else []) + [main_emb])
-        fps = torch.full((n_obj + (3 if do_cfg else 2),), float(target_fps), dtype=torch.float32, device=self.device)
+        main_lats, main_embs = [main_lat], [main_emb]
+        for k in range(1, nvar):  # a variant that shows variant 0's main image shares its draw and its vision-tower pass
+            if prompt_embeds is None:
+                pk, nk = c.encode_prompt(prompts[k], negs[k])
+                pes.append(pk), nes.append(nk)
+            main_lats.append(main_lat if mains_first[k] is main_first_image else image_latents(mains_first[k]))
+            main_embs.append(main_emb if mains_list[k] is main_image_list
+                             else encode_frames(list(mains_list[k])).transpose(0, 1))
+        ndst = 2 if do_cfg else 1
+        # batch order [bg, obj_1.., u_1..u_K, c_1..c_K] (variant_layout; K = 1: the reference's [bg, obj_1.., uncond, cond])
+        ehs = torch.cat([inv_pe.repeat(n_obj + 1, 1, 1)] + (nes if do_cfg else []) + pes)
+        first_all = torch.cat([bg_lat] + obj_first + main_lats * ndst)
+        lat_all = torch.cat([bg_lat2] + obj_lat + main_lats * ndst)
+        emb_all = torch.cat(embs[:-1] + ([torch.zeros_like(e) for e in main_embs] if do_cfg else []) + main_embs)
+        fps = torch.full((n_obj + 1 + ndst * nvar,), float(target_fps), dtype=torch.float32, device=self.device)
         cond = dict(encoder_hidden_states=ehs.to(self.device, H16).contiguous(), image_embeddings=emb_all.to(self.device, H16).contiguous(),
                     image_latents_first=first_all.to(self.device, H16).contiguous(), image_latents=lat_all.to(self.device, H16).contiguous(), fps=fps)
 
@@ -697,11 +812,21 @@ class I2VGenXLPipeline:
         sched.timesteps = sched.timesteps[ddim_init_latents_t_idx:]
         offs = obj_ddim_latents_idx_offset or [0] * n_obj
         fusion_ts = [[int(full.timesteps[offs[j]:][k]) for k in range(*fusion_steps)] for j in range(n_obj)]
-        latents = self.prepare_latents(1, 4, num_frames, height, width, H16, self.device, generator, latents)
+        latents = torch.cat([self.prepare_latents(1, 4, num_frames, height, width, H16, self.device, gens[k],
+                                                  None if latents is None else latents[k:k + 1]) for k in range(nvar)])
         if obj_masks_tensors is None:
             obj_masks_tensors = [mask_preprocess(m, self.device, H16, 1, 4, num_frames, downscale=8) for m in obj_mask]
-        st = self.make_composition_state(latents, cond, obj_masks_tensors, guidance_scale)
+        st = self.make_composition_state(latents, cond, obj_masks_tensors, scales if nvar > 1 else guidance_scale, variants=nvar)
         table, index = sched.coef_table(self.device, guidance_scale)
+        if nvar > 1:  # [steps, K, 5]: a step's coefficient rows are one view, whatever K is
+            table = torch.stack([sched.coef_table(self.device, g)[0] for g in scales], 1).contiguous()
+            nb = st["nb"]
+            if crosses_gemm_offset_line(nb, num_frames, latents.shape[-2], latents.shape[-1], self.unet.config.block_out_channels[0]) \
+                    and not getattr(self, "_warned_gemm_line", False):
+                self._warned_gemm_line = True
+                logger.warning("composition of %d variants: UNet batch %d puts the widest level-0 tensor at 2 GB or more; the "
+                               "eight-phase GEMM tiles (32-bit offsets) step aside for the general tiles there (DESIGN.md 6i)",
+                               nvar, nb)
         cache = self.latent_cache
         fusion_counter = 0  # never incremented in the reference (:1634, 1649)
         for i, t in enumerate(sched.timesteps):

@@ -331,15 +331,19 @@ class Transformer2DModel(_TransformerBase):
             masks = eng.device_masks(proc.mask)[1]  # bool masks as {0,1} fp16
             ld = qkv.stride(0)
             ops.pnp_blend_tokens(q, masks, x2=k, frames=F, height=H, width=W, channels=c, chunk_stride=F * hw * ld,
-                                 f_stride=hw * ld, p_stride=ld, base_chunk0=proc.inject_background, ndst=ndst, src_map=smap)
+                                 f_stride=hw * ld, p_stride=ld, base_chunk0=proc.inject_background, ndst=ndst, src_map=smap,
+                                 nvar=eng.variants)
         if ndst == 2 and eng.pair_destinations:
             # the injection has just written ONE blended q / k into both destination chunks (pnp_utils.py:664-668): their
             # softmax(q k^T) is the same matrix -- computed once, multiplied into the two chunks' own v (bit-identical outputs)
             a = torch.empty((nimg * hw, c), dtype=H16, device=x.device)
-            ns, rows = (B - 2) * F, F * hw
+            # (variants: the u block [u_1..u_K] pairs with the c block [c_1..c_K] at a constant offset -- one launch for K pairs)
+            nv = eng.variants
+            ns, rows = (B - 2 * nv) * F, nv * F * hw
             s0, s1, s2 = slice(0, ns * hw), slice(ns * hw, ns * hw + rows), slice(ns * hw + rows, ns * hw + 2 * rows)
             ops.flash_attn(q[s0], k[s0], v[s0], nbatch=ns, heads=self.heads, tq=hw, tk=hw, out=a[s0])
-            ops.flash_attn(q[s1], k[s1], v[s1], nbatch=F, heads=self.heads, tq=hw, tk=hw, out=a[s1], v2=v[s2], out2=a[s2])
+            ops.flash_attn(q[s1], k[s1], v[s1], nbatch=nv * F, heads=self.heads, tq=hw, tk=hw, out=a[s1], v2=v[s2],
+                           out2=a[s2])
         else:
             a = ops.flash_attn(q, k, v, nbatch=nimg, heads=self.heads, tq=hw, tk=hw)
         h = blk.attn1.to_out(a, resid=h, rowmom=True)
@@ -403,11 +407,11 @@ class TransformerTemporalModel(_TransformerBase):
                 ld = qkv.stride(0)
                 ops.pnp_blend_tokens(q, masks, x2=k, frames=F, height=H, width=W, channels=c, chunk_stride=F * hw * ld,
                                      f_stride=hw * ld, p_stride=ld, base_chunk0=proc.inject_background, ndst=ndst,
-                                     src_map=smap)
+                                     src_map=smap, nvar=eng.variants)
                 if eng._tail_site is self:  # (prune_source_tail) the last reader of the source chunks was this blend
-                    r0 = (B - ndst) * F * hw
+                    r0 = (B - ndst * eng.variants) * F * hw
                     q, k, v, h, x = q[r0:], k[r0:], v[r0:], h[r0:], x[r0:]
-                    B = ndst
+                    B = ndst * eng.variants
             a = ops.temporal_attn(q, k, v, nsample=B, frames=F, hw=hw, heads=self.heads)
             h = attn.to_out(a, resid=h, rowmom=True)
         f1 = blk.ff1.call_ln(h, blk.norm3, act=ACT_GEGLU)
@@ -612,6 +616,12 @@ class I2VGenXLUNet:
         # blend kernel.  Set and restored around its forward by the composition loop, like shared_prefix_chunks; the identity
         # map is today's path.  Not with a frame shard.
         self.source_chunks = None
+        # K variants over one set of sources (pipeline.py): the batch is [s_0..s_{nsrc-1}, u_1..u_K, c_1..c_K]
+        # ([s.., c_1..c_K] with guidance off) -- K destination pairs that differ in prompt / latents share the source chunks.
+        # Every injection site then calls the _variants blend entries (the sources read once, ndst*K chunks written) and the
+        # paired attention serves the K pairs in one launch.  1 = today's batch, kernels and launches.  Set and restored around
+        # its forward by the composition loop, like source_chunks.  Not with a frame shard, not with shared_prefix_chunks.
+        self.variants = 1
 
     def set_frame_shard(self, shard):
         """Frame-shard every forward over the ranks of ``shard`` (``mvoc_amd.frame_shard``): each rank receives the FULL
@@ -741,11 +751,20 @@ class I2VGenXLUNet:
 
     # ---- PnP helpers ------------------------------------------------------------------------------
     @staticmethod
-    def check_pnp_batch(B, mask_list, nsrc=None):
+    def check_pnp_batch(B, mask_list, nsrc=None, variants=1):
         """the hooks address chunks positionally [bg, obj_1..obj_n, uncond, cond] (pnp_utils.py:592 hard-codes 5); with
         classifier-free guidance off the batch is [bg, obj_1..obj_n, cond].  ``nsrc``: the number of source
         chunks of a source-de-duplicated batch (``source_chunks``; None = n_objects + 1).  Returns the number of trailing
-        destination chunks (2 or 1)."""
+        destination chunks (2 or 1).  ``variants`` = K > 1: the batch carries K destination
+        pairs (or K conditional chunks) behind the sources, B = nsrc + ndst * K; the return value stays the chunks PER variant."""
+        if variants != 1:
+            ns = nsrc if nsrc is not None else (None if mask_list is None else len(mask_list) + 1)
+            if not 1 <= variants <= 8:
+                raise RuntimeError(f"variants = {variants}: 1 to 8 variants share one set of source chunks")
+            if ns is None or B - ns not in (variants, 2 * variants):
+                raise RuntimeError(f"PnP injection is active but the UNet batch is {B}, expected the {ns} source chunks + "
+                                   f"{2 * variants} ([s.., u_1..u_{variants}, c_1..c_{variants}]) or + {variants} with guidance off")
+            return (B - ns) // variants
         if nsrc is None:
             if mask_list is None or B - len(mask_list) - 1 not in (1, 2):
                 raise RuntimeError(f"PnP injection is active but the UNet batch is {B}, expected n_objects+3 = "
@@ -776,7 +795,12 @@ class I2VGenXLUNet:
         smap = self.pnp_src_map()
         if smap is not None and len(smap[1]) != len(mask_list):
             raise RuntimeError(f"source_chunks maps {len(smap[1])} objects, the hooks carry {len(mask_list)} masks")
-        return self.check_pnp_batch(B, mask_list, None if smap is None else smap[0]), smap
+        if self.variants != 1:
+            if self.shard is not None:
+                raise RuntimeError("variants > 1 do not combine with the frame shard: run one composition per call")
+            if self.shared_prefix_chunks:
+                raise RuntimeError("variants > 1 do not combine with shared_prefix_chunks (DESIGN.md 6i)")
+        return self.check_pnp_batch(B, mask_list, None if smap is None else smap[0], self.variants), smap
 
     def device_masks(self, mask_list):
         """list of (float [1,4,F,h,w], bool [1,4,F,h,w]) pairs (``register_time_all``'s ``mask``) ->
@@ -846,7 +870,7 @@ class I2VGenXLUNet:
         hard = self.section_masks(mask_list, 1, full_hw) if full_hw is not None else self.device_masks(mask_list)[1]
         ld = h.stride(0)
         ops.pnp_blend_tokens(h, hard, frames=F, height=H, width=W, channels=channels, chunk_stride=F * H * W * ld,
-                             f_stride=H * W * ld, p_stride=ld, base_chunk0=True, ndst=ndst, src_map=smap)
+                             f_stride=H * W * ld, p_stride=ld, base_chunk0=True, ndst=ndst, src_map=smap, nvar=self.variants)
         if getattr(h, "chan_sums", None) is not None:
             h.chan_sums = None  # rewritten in place: the producer's GroupNorm statistics no longer describe these rows
 
@@ -992,7 +1016,7 @@ class I2VGenXLUNet:
         B, C, F, H, W = sample.shape
         co = self.conv_out
         ndst, smap = self.pnp_batch(B, co.mask)
-        ns = B - ndst
+        ns = B - ndst * self.variants
         cut = lambda t, per=1: None if t is None else (t if (not torch.is_tensor(t)) or t.dim() == 0 or t.shape[0] != B * per
                                                        else t[:ns * per])
         cond = None
@@ -1014,7 +1038,8 @@ class I2VGenXLUNet:
             self._pruned = False
         nchw = torch.empty((B * F, C, H, W), dtype=H16, device=self.device)
         nchw[:ns * F] = src.permute(0, 2, 1, 3, 4).reshape(ns * F, C, H, W)
-        ops.pnp_blend_nchw(nchw, self.device_masks(co.mask)[1], frames=F, base_chunk0=True, ndst=ndst, src_map=smap)
+        ops.pnp_blend_nchw(nchw, self.device_masks(co.mask)[1], frames=F, base_chunk0=True, ndst=ndst, src_map=smap,
+                           nvar=self.variants)
         return nchw.reshape(B, F, C, H, W).permute(0, 2, 1, 3, 4).contiguous()
 
     def spatial_transformers(self):
@@ -1134,7 +1159,8 @@ class I2VGenXLUNet:
             # so this tiny tensor goes through the NCHW form of the kernel on the boundary layout instead
             out = ops.tokens_to_ncfhw(y, B, co.cout, F, H, W)  # [B,C,F,h,w]
             nchw = out.permute(0, 2, 1, 3, 4).reshape(B * F, co.cout, H, W).contiguous()
-            ops.pnp_blend_nchw(nchw, self.device_masks(co.mask)[1], frames=F, base_chunk0=True, ndst=ndst, src_map=smap)
+            ops.pnp_blend_nchw(nchw, self.device_masks(co.mask)[1], frames=F, base_chunk0=True, ndst=ndst, src_map=smap,
+                               nvar=self.variants)
             out = nchw.reshape(B, F, co.cout, H, W).permute(0, 2, 1, 3, 4).contiguous()
         else:
             out = ops.tokens_to_ncfhw(y, B, co.cout, F, H, W)

@@ -12,6 +12,9 @@ CLIP / file entry points with synchronising timers (IO excluded from 
 
 Used by `bench.py --workload demo`; prints one JSON object.  usage: python tools/demo_job.py [--frames 16] [--size 512] [--steps 50]
 
+--variants K (opt-in): K prompts and seeds over the job's three sources in ONE composition loop (an entry with `variants`,
+DESIGN.md 6i); the JSON line holds the composition-stage time and the mean device time of a step of each kind.
+
 --shared-source (opt-in): the shape of MVOC's own demo entries, where the background and both objects point at ONE inversion
 directory and the same control frames.  One clip is inverted, then the composition runs with source de-duplication off and then
 on (composite.py --dedup_sources), in this process; the JSON line holds both composition-stage times (the sampling call without
@@ -261,6 +264,132 @@ def run_shared_source(frames=16, size=512, steps=50, keep=False):
     }
 
 
+VARIANT_PROMPTS = ("windsurf,sailboat,sky,ocean", "kayak,paddle,lake,mist", "sailboat,sunset,orange sky", "surfer,wave,storm clouds",
+                   "rowing boat,river,reeds", "catamaran,lagoon,noon", "canoe,fjord,snow", "raft,rapids,canyon")
+
+
+def boat_surf_entry(size):
+    """the boat_surf-shaped composition entry over the three clips of ``write_tree`` (three distinct sources)"""
+    lat = "inversions/i2vgen-xl/{}/ddim_latents"
+    return {"active": True, "task_name": "demo", "video_name": "bg_clip", "editing_prompt": VARIANT_PROMPTS[0],
+            "editing_negative_prompt": "Chaotic, chaotic colors", "edited_video_name": "out",
+            "edited_first_frame_path": "demo/bg_clip/edited_first_frame/00000.png",
+            "ddim_init_latents_t_idx": 0, "pnp_f_t": 0.1, "pnp_spatial_attn_t": 1.0, "pnp_temp_attn_t": 1.0, "random_noise_ratio": 0.0,
+            "fusion_step": [0, 1], "obj_mask_path": ["demo/bg_clip/m1", "demo/bg_clip/m2"], "obj_width_height": [[size, size], [size, size]],
+            "obj_ddim_latents_path": [lat.format("obj1_clip"), lat.format("obj2_clip")], "bg_ddim_latents_path": lat.format("bg_clip"),
+            "edited_contorl_frame_path_main": "demo/bg_clip/bg_clip", "edited_contorl_frame_path_background": "demo/bg_clip/bg_clip",
+            "edited_contorl_frame_path": ["demo/obj1_clip/obj1_clip", "demo/obj2_clip/obj2_clip"]}
+
+
+class StageTimer:
+    """the sampling call's wall-clock without the VAE decode (as --shared-source reports it), and the device time of every
+    composition step by kind (CUDA events around ``composition_step``; the first step of a kind, which warms up and captures
+    its graph, is left out of the mean)"""
+
+    NAME = "sample_with_pnp_pipeline_with_edit_prompt_extraction_with_attn_injection"
+
+    def __init__(self, pl):
+        self.pl, self.sample_s, self.decode_s, self.steps = pl, 0.0, 0.0, []
+        self._orig = (getattr(pl.I2VGenXLPipeline, self.NAME), pl.I2VGenXLPipeline._to_video, pl.I2VGenXLPipeline.composition_step)
+
+    def __enter__(self):
+        sample_fn, to_video, step_fn = self._orig
+        timer = self
+
+        def timed_sample(self, *a, **kw):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            try:
+                return sample_fn(self, *a, **kw)
+            finally:
+                torch.cuda.synchronize()
+                timer.sample_s += time.perf_counter() - t0
+
+        def timed_decode(self, latents, output_type):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            try:
+                return to_video(self, latents, output_type)
+            finally:
+                torch.cuda.synchronize()
+                timer.decode_s += time.perf_counter() - t0
+
+        def timed_step(self, *a, **kw):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = step_fn(self, *a, **kw)
+            e1.record()
+            timer.steps.append(("conv_out_injection" if self.unet.conv_out.injecting() else "qk", e0, e1))
+            return out
+
+        P = self.pl.I2VGenXLPipeline
+        setattr(P, self.NAME, timed_sample)
+        P._to_video, P.composition_step = timed_decode, timed_step
+        return self
+
+    def __exit__(self, *exc):
+        P = self.pl.I2VGenXLPipeline
+        setattr(P, self.NAME, self._orig[0])
+        P._to_video, P.composition_step = self._orig[1], self._orig[2]
+
+    def result(self):
+        torch.cuda.synchronize()
+        by, seen = {}, set()
+        for kind, e0, e1 in self.steps:
+            if kind not in seen:  # warm-up + capture
+                seen.add(kind)
+                continue
+            by.setdefault(kind, []).append(e0.elapsed_time(e1))
+        return {"composition_s": round(self.sample_s - self.decode_s, 3),
+                "mean_step_ms": {k: round(sum(v) / len(v), 3) for k, v in sorted(by.items())},
+                "steps_timed": {k: len(v) for k, v in sorted(by.items())}}
+
+
+def run_variants(frames=16, size=512, steps=50, keep=False, variants=2):
+    """K prompts and seeds over the boat_surf-shaped job (three distinct sources), one composition loop (composite.py `variants`)"""
+    composite, inverse, _ = _import_drivers()
+    from mvoc_amd.config import OmegaConf
+    from mvoc_amd import pipeline as pl
+    if not 1 <= variants <= len(VARIANT_PROMPTS):
+        raise SystemExit(f"--variants {variants}: 1 to {len(VARIANT_PROMPTS)}")
+    root = tempfile.mkdtemp(prefix="mvoc_demo_variants_")
+    write_tree(root, frames, size)
+    dev = torch.device("cuda:0")
+    it = OmegaConf.load(os.path.join(REPO, "tests", "data", "inversion_template.yaml"))
+    it.data_dir = root
+    it.image_size = [size, size]
+    it.n_frames = frames
+    it.inverse_config.n_steps = steps
+    entries = [{"active": True, "force_recompute_latents": True, "video_name": n, "video_dir": os.path.join(root, "demo", n),
+                "recon_config": {"enable_recon": False}} for n in ("bg_clip", "obj1_clip", "obj2_clip")]
+    inverse.main(it, entries, dev, synthetic=True)
+    torch.cuda.synchronize()
+    ct = OmegaConf.load(os.path.join(REPO, "tests", "data", "composite_template.yaml"))
+    ct.data_dir = root
+    ct.image_size = [size, size]
+    ct.n_frames = frames
+    ct.n_steps = steps
+    centry = dict(boat_surf_entry(size), variants=[{"editing_prompt": VARIANT_PROMPTS[k], "seed": 6 + k} for k in range(variants)])
+    with StageTimer(pl) as timer:
+        composite.main(ct, [centry], dev, synthetic=True)
+    res = timer.result()
+    out_root = os.path.join(root, "Results", "demo", "i2vgen-xl", "bg_clip", "out")
+    suffix = os.listdir(out_root)[0]
+    dirs = sorted(os.listdir(os.path.join(out_root, suffix)))
+    files = {d: sorted(os.listdir(os.path.join(out_root, suffix, d))) for d in dirs}
+    if not keep:
+        shutil.rmtree(root, ignore_errors=True)
+    n_obj = 2
+    return dict(res, job=f"3 x {steps}-step DDIM inversion ({frames} frames, {size}x{size}) + ONE {steps}-step PnP composition loop of "
+                         f"{variants} variants (prompts, seeds) over bg + 2 objects, composite.py `variants`, seeded synthetic weights",
+                variants=variants, unet_batch={"qk": n_obj + 1 + 2 * variants, "conv_out_injection": n_obj + 1},
+                chunk_count_expectation_vs_sequential={"qk": round((n_obj + 1 + 2 * variants) / (variants * (n_obj + 3)), 3),
+                                                       "conv_out_injection": round(1 / variants, 3)},
+                output_dirs=dirs, n_result_files={d: len(f) for d, f in files.items()}, result_files=files[dirs[0]][:3],
+                note="composition stage = the sampling call without the VAE decode (conditioning encoders, graph capture and the "
+                     "denoising loop); mean_step_ms = device time of composition_step by kind, the capturing step of each kind left out")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=16)
@@ -269,7 +398,12 @@ if __name__ == "__main__":
     ap.add_argument("--keep", action="store_true")
     ap.add_argument("--shared-source", action="store_true",
                     help="one source behind every role: the composition without and with source de-duplication")
+    ap.add_argument("--variants", type=int, default=0, metavar="K",
+                    help="K prompts and seeds over the job's three sources in one composition loop (composite.py `variants`)")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
-    fn = run_shared_source if a.shared_source else run
-    print(json.dumps(fn(a.frames, a.size, a.steps, a.keep)), flush=True)
+    if a.variants:
+        print(json.dumps(run_variants(a.frames, a.size, a.steps, a.keep, a.variants)), flush=True)
+    else:
+        fn = run_shared_source if a.shared_source else run
+        print(json.dumps(fn(a.frames, a.size, a.steps, a.keep)), flush=True)
