@@ -8,7 +8,8 @@ keys, hook registration order and output naming as the reference's ``i2vgen-xl/c
 
 ``--dedup_sources``: roles (background, objects) that are the same source share one UNet chunk.
 An entry with ``variants: [{...}, ...]`` composes K prompts / seeds / guidance scales over its sources in one loop
-(``merge_variants``; files under ``.../variant_00/``, ``variant_01/`` ...).
+(``merge_variants``; files under ``.../variant_00/``, ``variant_01/`` ...); a variant's ``pnp: {...}`` gives it injection
+thresholds of its own.
 """
 import argparse
 import json
@@ -26,20 +27,28 @@ from mvoc_amd.launch import my_entries, pick_device
 from mvoc_amd.schedulers import DDIMScheduler
 from pipelines.pipeline_i2vgen_xl import I2VGenXLPipeline, I2VGenXLUnetExtension
 from pnp_utils import (modify_diffuser_attention_forward, register_out_conv_injection, register_resnet_injection,
-                       register_spatial_attention_pnp, register_temp_attention_pnp, register_temp_conv_injection)
+                       register_spatial_attention_pnp, register_temp_attention_pnp, register_temp_conv_injection,
+                       register_variant_schedules)
 from utils import export_to_gif, load_image, seed_everything
 
 logger = logging.getLogger(__name__)
 
 
-def init_pnp(pipe, scheduler, config):
-    """injection schedules are prefixes of the FULL timestep list (``composite.py:38-60``), registered in the
-    reference's order: forward patch, temporal attn, spatial attn, temporal conv, conv_out, resnet"""
+def _schedule_prefixes(scheduler, config):
     n = config.n_steps
     conv_t, spa_t, tmp_t = int(n * config.pnp_f_t), int(n * config.pnp_spatial_attn_t), int(n * config.pnp_temp_attn_t)
     conv_ts = scheduler.timesteps[:conv_t] if conv_t >= 0 else []
     spa_ts = scheduler.timesteps[:spa_t] if spa_t >= 0 else []
     tmp_ts = scheduler.timesteps[:tmp_t] if tmp_t >= 0 else []
+    return (conv_t, spa_t, tmp_t), (conv_ts, spa_ts, tmp_ts)
+
+
+def init_pnp(pipe, scheduler, config, variants=None):
+    """injection schedules are prefixes of the FULL timestep list (``composite.py:38-60``), registered in the
+    reference's order: forward patch, temporal attn, spatial attn, temporal conv, conv_out, resnet.  ``variants``: the merged
+    configs of the entry's variants (``merge_variants``); when one of them carries thresholds of its own (``pnp``) every
+    variant's prefixes are registered on top (``register_variant_schedules``), by the same ``int(n * t)`` rule."""
+    (conv_t, spa_t, tmp_t), (conv_ts, spa_ts, tmp_ts) = _schedule_prefixes(scheduler, config)
     modify_diffuser_attention_forward(pipe.unet)
     register_temp_attention_pnp(pipe, tmp_ts, config.inject_background)
     register_spatial_attention_pnp(pipe, spa_ts, config.inject_background)
@@ -47,6 +56,11 @@ def init_pnp(pipe, scheduler, config):
     register_out_conv_injection(pipe, conv_ts)
     register_resnet_injection(pipe, conv_ts)
     logger.debug(f"conv/spatial/temporal injection steps: {conv_t}/{spa_t}/{tmp_t}")
+    if variants is not None and any("pnp" in c for c in variants):
+        per = [_schedule_prefixes(scheduler, c) for c in variants]
+        register_variant_schedules(pipe, conv=[p[1][0] for p in per], spatial=[p[1][1] for p in per],
+                                   temporal=[p[1][2] for p in per])
+        logger.debug(f"per-variant conv/spatial/temporal injection steps: {[p[0] for p in per]}")
 
 
 def _frames(folder, n, size):
@@ -63,10 +77,12 @@ def output_suffix(config):
             + f"{config.fusion_step[0]}-{config.fusion_step[1]}")
 
 
-# what one variant of an entry may override; every other key is shared by the variants of a call (sources, masks, schedules,
-# fusion settings: the source chunks are computed once for all of them)
+# what one variant of an entry may override; every other key is shared by the variants of a call (sources, masks, the entry's
+# schedules, fusion settings: the source chunks are computed once for all of them).  "pnp" is a dict of injection thresholds
+# of the variant's own (any of PNP_KEYS) -- the flat threshold keys stay the entry's
 VARIANT_KEYS = ("editing_prompt", "editing_negative_prompt", "seed", "cfg", "edited_first_frame_path",
-                "edited_contorl_frame_path_main")
+                "edited_contorl_frame_path_main", "pnp")
+PNP_KEYS = ("pnp_f_t", "pnp_spatial_attn_t", "pnp_temp_attn_t")
 MAX_VARIANTS = 8
 
 
@@ -88,8 +104,9 @@ def resolve_config(template_config, entry):
 
 def merge_variants(template_config, entry):
     """An entry may carry ``variants: [{...}, ...]``: K compositions over the entry's sources in one loop, each dict overriding
-    any of ``VARIANT_KEYS``.  -> (config, None) for an entry without the key -- exactly the single composition -- else
-    (the entry's own config, [merged config of variant k]).  Overriding a shared key is an error that names it."""
+    any of ``VARIANT_KEYS`` (``pnp``: a dict over ``PNP_KEYS``, the variant's own injection thresholds).  -> (config, None)
+    for an entry without the key -- exactly the single composition -- else (the entry's own config, [merged config of
+    variant k]).  Overriding a shared key is an error that names it."""
     entry = dict(entry)
     variants = entry.pop("variants", None)
     config = resolve_config(template_config, entry)
@@ -103,7 +120,12 @@ def merge_variants(template_config, entry):
             if key not in VARIANT_KEYS:
                 raise ValueError(f"variants[{k}] overrides '{key}', which all variants of an entry share; a variant may set "
                                  f"{', '.join(VARIANT_KEYS)}")
-        merged.append(resolve_config(template_config, {**entry, **dict(v)}))
+        pnp = dict(v.get("pnp") or {})
+        for key in pnp:
+            if key not in PNP_KEYS:
+                raise ValueError(f"variants[{k}].pnp sets '{key}'; the per-variant injection thresholds are {', '.join(PNP_KEYS)}")
+        # the thresholds land on the variant's merged config: output_suffix / variant_output_dir show the variant's own
+        merged.append(resolve_config(template_config, {**entry, **dict(v), **pnp}))
     return config, merged
 
 
@@ -137,7 +159,7 @@ def main(template_config, configs_list, device, synthetic=False, dedup_sources=F
         obj_frames = [_frames(p, config.n_frames, config.image_size) for p in config.edited_contorl_frame_path]
         bg_frames = _frames(config.edited_contorl_frame_path_background, config.n_frames, config.image_size)
         ddim_scheduler.set_timesteps(config.n_steps)
-        init_pnp(pipe, ddim_scheduler, config)
+        init_pnp(pipe, ddim_scheduler, config, variants)
         pipe.register_modules(scheduler=ddim_scheduler)
         pipe.unet.forward = partial(I2VGenXLUnetExtension.forward, pipe.unet)
         out_type = "pil"

@@ -318,6 +318,16 @@ int mvoc_pnp_blend_scatter_tokens_variants(const mvoc_pnp_desc* d, int32_t nsrc,
                                            void* stream);
 int mvoc_pnp_blend_scatter_nchw_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
                                          void* stream);
+/* Per-variant injection schedules: the _variants entries with a bitmask -- bit k of `active` set = variant k
+ * injects at this launch.  An injecting variant's u_k / c_k rows are what the _variants entry writes; the chunks of every other
+ * variant are neither read nor written.  `active` travels by value in the kernel arguments (no device array: a captured graph
+ * replays it).  Traffic per tensor: distinct sources read (+ popcount(active) bases when base_chunk0 == 0) +
+ * ndst * popcount(active) chunks written.
+ * Requires 1 <= nvar <= 8, 1 <= active < (1u << nvar) and a valid map (else -1 and an error text, nothing written). */
+int mvoc_pnp_blend_scatter_tokens_variants_sel(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
+                                               uint32_t active, void* stream);
+int mvoc_pnp_blend_scatter_nchw_variants_sel(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
+                                             uint32_t active, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Loop glue on [B,4,F,h,w] fp16 latents, BIT-EXACT vs the reference's eager fp16 op chain.

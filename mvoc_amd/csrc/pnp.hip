@@ -250,6 +250,113 @@ __global__ __launch_bounds__(256) void pnp_nchw_variants_kernel(const PnpArgs p,
   }
 }
 
+// ---- per-variant injection schedules -----------------------------------------------------------
+// The variants kernels with a by-value bitmask: bit k of `active` set = variant k injects at this launch.  The chunks of a
+// variant whose bit is clear are neither read nor written; the skip is wave-uniform (a kernel argument).  Kernels of their
+// own, so the instantiations above compile as they always did.
+template <int NOBJ>
+__global__ __launch_bounds__(256) void pnp_tokens_variants_sel_kernel(const PnpArgs p, const int nvar, const unsigned active) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= p.total) return;
+  half_t* x = p.x[blockIdx.y];
+  const int c8n = p.channels >> 3;
+  const int c8 = (int)(idx % c8n);
+  const long fp = idx / c8n;
+  const int hw = p.height * p.width;
+  const int f = (int)(fp / hw), px = (int)(fp % hw);
+  const int py = px / p.width, pxx = px - py * p.width;
+  const int my = nearest_src(py, p.sy, p.mask_h), mx = nearest_src(pxx, p.sx, p.mask_w);
+  const long off = (long)f * p.f_stride + (long)px * p.p_stride + c8 * 8;
+  half8_t ov[NOBJ];
+  float m[NOBJ];
+#pragma unroll
+  for (int j = 0; j < NOBJ; ++j) {
+    m[j] = (float)p.masks[(((long)j * p.frames + f) * p.mask_h + my) * p.mask_w + mx];
+    ov[j] = *reinterpret_cast<const half8_t*>(x + obj_chunk<true>(p, j) * p.chunk_stride + off);
+  }
+  half8_t o;
+  if (p.base_chunk0) {  // one blend for every injecting variant
+    const half8_t bv = *reinterpret_cast<const half8_t*>(x + off);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float inj = (float)bv[e];
+#pragma unroll
+      for (int j = 0; j < NOBJ; ++j) inj = blend16(inj, (float)ov[j][e], m[j]);
+      o[e] = (half_t)inj;
+    }
+  }
+  for (int k = 0; k < nvar; ++k) {
+    if (!((active >> k) & 1u)) continue;
+    half_t* cond = x + var_dst(p, nvar, p.ndst - 1, k) * p.chunk_stride + off;
+    if (!p.base_chunk0) {
+      const half8_t bv = *reinterpret_cast<const half8_t*>(cond);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        float inj = (float)bv[e];
+#pragma unroll
+        for (int j = 0; j < NOBJ; ++j) inj = blend16(inj, (float)ov[j][e], m[j]);
+        o[e] = (half_t)inj;
+      }
+    }
+    if (p.ndst == 2) *reinterpret_cast<half8_t*>(x + var_dst(p, nvar, 0, k) * p.chunk_stride + off) = o;
+    *reinterpret_cast<half8_t*>(cond) = o;
+  }
+}
+
+template <int VEC, int NOBJ>
+__global__ __launch_bounds__(256) void pnp_nchw_variants_sel_kernel(const PnpArgs p, const int nvar, const unsigned active) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= p.total) return;
+  half_t* x = p.x[blockIdx.y];
+  const int hw = p.height * p.width;
+  const int pvn = hw / VEC;
+  const int pv = (int)(idx % pvn);
+  const long fc = idx / pvn;
+  const int f = (int)(fc / p.channels);
+  const long off = fc * hw + (long)pv * VEC;  // (f*C + c)*HW + p
+  const long chunk = (long)p.frames * p.channels * hw;
+  half_t ov[NOBJ][VEC];
+  float m[NOBJ][VEC];
+#pragma unroll
+  for (int j = 0; j < NOBJ; ++j) {
+    ld_vec<VEC>(ov[j], x + obj_chunk<true>(p, j) * chunk + off);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      const int px = pv * VEC + e;
+      const int py = px / p.width, pxx = px - py * p.width;
+      const int my = nearest_src(py, p.sy, p.mask_h), mx = nearest_src(pxx, p.sx, p.mask_w);
+      m[j][e] = (float)p.masks[(((long)j * p.frames + f) * p.mask_h + my) * p.mask_w + mx];
+    }
+  }
+  half_t tmp[VEC];
+  if (p.base_chunk0) {
+    ld_vec<VEC>(tmp, x + off);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      float inj = (float)tmp[e];
+#pragma unroll
+      for (int j = 0; j < NOBJ; ++j) inj = blend16(inj, (float)ov[j][e], m[j][e]);
+      tmp[e] = (half_t)inj;
+    }
+  }
+  for (int k = 0; k < nvar; ++k) {
+    if (!((active >> k) & 1u)) continue;
+    half_t* cond = x + var_dst(p, nvar, p.ndst - 1, k) * chunk + off;
+    if (!p.base_chunk0) {
+      ld_vec<VEC>(tmp, cond);
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        float inj = (float)tmp[e];
+#pragma unroll
+        for (int j = 0; j < NOBJ; ++j) inj = blend16(inj, (float)ov[j][e], m[j][e]);
+        tmp[e] = (half_t)inj;
+      }
+    }
+    if (p.ndst == 2) st_vec<VEC>(x + var_dst(p, nvar, 0, k) * chunk + off, tmp);
+    st_vec<VEC>(cond, tmp);
+  }
+}
+
 int fill_args(const mvoc_pnp_desc* d, PnpArgs& a) {
   MVOC_REQUIRE(d && d->x && d->masks, -1, "pnp: null operand");
   MVOC_REQUIRE(d->nobj >= 1 && d->nobj <= 4, -2, "pnp: nobj %d not in [1,4]", d->nobj);
@@ -480,6 +587,81 @@ extern "C" int mvoc_pnp_blend_scatter_nchw_variants(const mvoc_pnp_desc* d, int3
     default: launch_nchw_variants_n<4>(vec, grid, s, a, nvar); break;
   }
   return mvoc_check_launch("pnp_nchw_variants_kernel");
+}
+
+namespace {
+
+// _sel: distinct sources read (+ one base per INJECTING variant unless the base is chunk 0), ndst chunks written per injecting variant
+int fill_variants_sel(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar, uint32_t active, PnpArgs& a,
+                      double& chunks) {
+  MVOC_REQUIRE(nvar >= 1 && nvar <= 8, -1, "pnp variants: nvar %d not in [1, 8]", nvar);
+  MVOC_REQUIRE(active != 0 && active < (1u << nvar), -1, "pnp variants: active mask 0x%x not in [1, 2^nvar = %u)", active,
+               1u << nvar);
+  int nread = 0;
+  if (int rc = fill_args(d, a)) return rc;
+  if (int rc = fill_map(d, nsrc, obj_chunk, a, nread)) return rc;
+  const int on = __builtin_popcount(active);
+  chunks = (d->base_chunk0 ? nread : nread - 1 + on) + (double)a.ndst * on;
+  return 0;
+}
+
+template <int NOBJ>
+void launch_nchw_variants_sel_n(bool vec, dim3 grid, hipStream_t s, const PnpArgs& a, int nvar, unsigned active) {
+  if (vec)
+    hipLaunchKernelGGL((pnp_nchw_variants_sel_kernel<8, NOBJ>), grid, dim3(256), 0, s, a, nvar, active);
+  else
+    hipLaunchKernelGGL((pnp_nchw_variants_sel_kernel<1, NOBJ>), grid, dim3(256), 0, s, a, nvar, active);
+}
+
+}  // namespace
+
+extern "C" int mvoc_pnp_blend_scatter_tokens_variants_sel(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
+                                                          int32_t nvar, uint32_t active, void* stream) {
+  PnpArgs a;
+  double chunks = 0;
+  if (int rc = fill_variants_sel(d, nsrc, obj_chunk, nvar, active, a, chunks)) return rc;
+  MVOC_REQUIRE(d->channels % 8 == 0 && d->chunk_stride % 8 == 0 && d->f_stride % 8 == 0 && d->p_stride % 8 == 0, -2,
+               "pnp tokens: channels/strides must be multiples of 8");
+  a.total = (long)d->frames * d->height * d->width * (d->channels / 8);
+  const long nblk = (a.total + 255) / 256;
+  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "pnp tokens: grid too large");
+  const int ntens = d->x2 ? 2 : 1;
+  hipStream_t s = (hipStream_t)stream;
+  const double elems = (double)d->frames * d->height * d->width * d->channels;
+  MvocProfScope prof(MVOC_FAM_PNP, s, ntens * (elems * 2.0 * chunks + 2.0 * d->nobj * d->frames * d->height * d->width));
+  const dim3 grid((unsigned)nblk, ntens);
+  const unsigned act = active;
+  switch (d->nobj) {
+    case 1: hipLaunchKernelGGL(pnp_tokens_variants_sel_kernel<1>, grid, dim3(256), 0, s, a, (int)nvar, act); break;
+    case 2: hipLaunchKernelGGL(pnp_tokens_variants_sel_kernel<2>, grid, dim3(256), 0, s, a, (int)nvar, act); break;
+    case 3: hipLaunchKernelGGL(pnp_tokens_variants_sel_kernel<3>, grid, dim3(256), 0, s, a, (int)nvar, act); break;
+    default: hipLaunchKernelGGL(pnp_tokens_variants_sel_kernel<4>, grid, dim3(256), 0, s, a, (int)nvar, act); break;
+  }
+  return mvoc_check_launch("pnp_tokens_variants_sel_kernel");
+}
+
+extern "C" int mvoc_pnp_blend_scatter_nchw_variants_sel(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
+                                                        int32_t nvar, uint32_t active, void* stream) {
+  PnpArgs a;
+  double chunks = 0;
+  if (int rc = fill_variants_sel(d, nsrc, obj_chunk, nvar, active, a, chunks)) return rc;
+  const long hw = (long)d->height * d->width;
+  const bool vec = hw % 8 == 0;
+  a.total = (long)d->frames * d->channels * (vec ? hw / 8 : hw);
+  const long nblk = (a.total + 255) / 256;
+  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "pnp nchw: grid too large");
+  const int ntens = d->x2 ? 2 : 1;
+  hipStream_t s = (hipStream_t)stream;
+  const double elems = (double)d->frames * hw * d->channels;
+  MvocProfScope prof(MVOC_FAM_PNP, s, ntens * (elems * 2.0 * chunks + 2.0 * d->nobj * d->frames * hw));
+  const dim3 grid((unsigned)nblk, ntens);
+  switch (d->nobj) {
+    case 1: launch_nchw_variants_sel_n<1>(vec, grid, s, a, nvar, active); break;
+    case 2: launch_nchw_variants_sel_n<2>(vec, grid, s, a, nvar, active); break;
+    case 3: launch_nchw_variants_sel_n<3>(vec, grid, s, a, nvar, active); break;
+    default: launch_nchw_variants_sel_n<4>(vec, grid, s, a, nvar, active); break;
+  }
+  return mvoc_check_launch("pnp_nchw_variants_sel_kernel");
 }
 
 extern "C" int mvoc_ddim_step_variants_f16(const void* x, const void* v_uncond, const void* v_cond, const float* coef_dev,

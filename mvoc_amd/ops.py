@@ -529,18 +529,37 @@ def _check_variants(x, x2, nvar, need, what):
                                f"(needs {need} elements from its first)")
 
 
+def _active_mask(active, nvar, what):
+    """``active`` (per-variant injection schedules) -> None when every variant injects (today's entries), else
+    the bitmask for the ``_sel`` entries"""
+    if active is None:
+        return None
+    active, nvar = int(active), int(nvar)
+    if not 1 <= nvar <= 8:
+        raise RuntimeError(f"{what}: variants {nvar} not in [1, 8]")
+    if not 1 <= active < (1 << nvar):
+        raise RuntimeError(f"{what}: active mask {active:#x} not in [1, 2^{nvar}): bit k set = variant k injects")
+    return None if active == (1 << nvar) - 1 else active
+
+
 def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride, f_stride, p_stride, x2=None,
-                     base_chunk0=False, ndst=2, src_map=None, nvar=1):
+                     base_chunk0=False, ndst=2, src_map=None, nvar=1, active=None):
     """In-place masked blend + scatter on channel-contiguous data (see include/mvoc_hip.h).  ``ndst``: trailing
     destination chunks (2 = [uncond, cond], 1 = [cond] with CFG off).  ``src_map`` = (nsrc, obj_chunks): the batch holds
     nsrc de-duplicated source chunks, object j reads chunk obj_chunks[j] (None: [bg, obj_1..obj_n], the unmapped entry).
-    ``nvar`` = K > 1: K variants share the sources, the batch is [s.., u_1..u_K, c_1..c_K] ([s.., c_1..c_K] with ndst 1)."""
+    ``nvar`` = K > 1: K variants share the sources, the batch is [s.., u_1..u_K, c_1..c_K] ([s.., c_1..c_K] with ndst 1).
+    ``active``: bit k set = variant k injects (None or all K bits: every variant, the entries of a call without it)."""
     d = _pnp_desc(x, x2, masks, chunk_stride, f_stride, p_stride, frames, height, width, channels, base_chunk0, ndst)
+    active = _active_mask(active, nvar, "pnp_blend_tokens")
     if nvar != 1:
         nsrc, chunks = _variant_map(src_map, d.nobj)
         last = (nsrc + (int(ndst) or 2) * int(nvar) - 1) * chunk_stride
         _check_variants(x, x2, nvar, last + (frames - 1) * f_stride + (height * width - 1) * p_stride + channels,
                         "pnp_blend_tokens")
+        if active is not None:
+            check(lib.mvoc_pnp_blend_scatter_tokens_variants_sel(C.byref(d), nsrc, chunks, int(nvar), active, _stream()),
+                  "pnp_blend_scatter_tokens_variants_sel")
+            return x
         check(lib.mvoc_pnp_blend_scatter_tokens_variants(C.byref(d), nsrc, chunks, int(nvar), _stream()),
               "pnp_blend_scatter_tokens_variants")
     elif src_map is None:
@@ -551,15 +570,21 @@ def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride,
     return x
 
 
-def pnp_blend_nchw(x, masks, *, frames, x2=None, base_chunk0=True, ndst=2, src_map=None, nvar=1):
+def pnp_blend_nchw(x, masks, *, frames, x2=None, base_chunk0=True, ndst=2, src_map=None, nvar=1, active=None):
     """In-place on x [(nobj+1+ndst)*F, C, H, W] (reference feature-map layout); with ``src_map`` = (nsrc, obj_chunks)
-    x is [(nsrc+ndst)*F, C, H, W], with ``nvar`` = K > 1 [(nsrc+ndst*K)*F, C, H, W] (see ``pnp_blend_tokens``)."""
+    x is [(nsrc+ndst)*F, C, H, W], with ``nvar`` = K > 1 [(nsrc+ndst*K)*F, C, H, W]; ``active`` picks the variants that are
+    written (see ``pnp_blend_tokens``)."""
     if x.dim() != 4 or not x.is_contiguous():
         raise RuntimeError("pnp_blend_nchw: x must be contiguous [N, C, H, W]")
     d = _pnp_desc(x, x2, masks, 0, 0, 0, frames, x.shape[2], x.shape[3], x.shape[1], base_chunk0, ndst)
+    active = _active_mask(active, nvar, "pnp_blend_nchw")
     if nvar != 1:
         nsrc, chunks = _variant_map(src_map, d.nobj)
         _check_variants(x, x2, nvar, (nsrc + (int(ndst) or 2) * int(nvar)) * frames * x[0].numel(), "pnp_blend_nchw")
+        if active is not None:
+            check(lib.mvoc_pnp_blend_scatter_nchw_variants_sel(C.byref(d), nsrc, chunks, int(nvar), active, _stream()),
+                  "pnp_blend_scatter_nchw_variants_sel")
+            return x
         check(lib.mvoc_pnp_blend_scatter_nchw_variants(C.byref(d), nsrc, chunks, int(nvar), _stream()),
               "pnp_blend_scatter_nchw_variants")
     elif src_map is None:

@@ -667,10 +667,11 @@ class I2VGenXLPipeline:
         if not self.use_graphs:
             b["body"]()
             return
-        # a captured iteration bakes in EVERY site's injecting() decision (the reference allows a schedule per site), the
-        # device copies of the masks and the batch's source map: all are part of the variant key
+        # a captured iteration bakes in EVERY site's injecting decision (the reference allows a schedule per site; with
+        # per-variant schedules, DESIGN.md 6j, a site's decision is the bitmask of its injecting variants -- 0 or all bits
+        # without them), the device copies of the masks and the batch's source map: all are part of the variant key
         u = self.unet
-        vkey = (u.injection_flags(), u.mask_key(st["masks"]), bool(u.pair_destinations), bool(u.prune_dead_chunks),
+        vkey = (u.injection_masks(st["nvar"]), u.mask_key(st["masks"]), bool(u.pair_destinations), bool(u.prune_dead_chunks),
                 bool(self.prune_source_tail), bool(st.get("share_cfg_prefix")), smap, st["nvar"])
         g = st["variants"].get(vkey)
         if g is None:
@@ -816,6 +817,7 @@ class I2VGenXLPipeline:
                                                   None if latents is None else latents[k:k + 1]) for k in range(nvar)])
         if obj_masks_tensors is None:
             obj_masks_tensors = [mask_preprocess(m, self.device, H16, 1, 4, num_frames, downscale=8) for m in obj_mask]
+        self.unet.check_variant_schedules(nvar)  # per-variant injection schedules are hook state (pnp_utils): one entry per variant
         st = self.make_composition_state(latents, cond, obj_masks_tensors, scales if nvar > 1 else guidance_scale, variants=nvar)
         table, index = sched.coef_table(self.device, guidance_scale)
         if nvar > 1:  # [steps, K, 5]: a step's coefficient rows are one view, whatever K is

@@ -59,14 +59,25 @@ def modify_diffuser_attention_forward(unet):
     return unet
 
 
-def _register_attn(model, injection_schedule, inject_background, temporal):
+def _attn_sites(model, temporal):
     for res, blocks in ATTN_SITES.items():
         for block in blocks:
             blk = model.unet.up_blocks[res]
             tr = (blk.temp_attentions if temporal else blk.attentions)[block]
-            proc = tr.transformer_blocks[0].attn1.processor
-            proc.injection_schedule = injection_schedule
-            proc.inject_background = inject_background
+            yield tr.transformer_blocks[0].attn1.processor
+
+
+def _feature_sites(model, kind):
+    for b in FEATURE_BLOCKS:
+        for i in FEATURE_LAYERS:
+            yield getattr(model.unet.up_blocks[b], kind)[i]
+
+
+def _register_attn(model, injection_schedule, inject_background, temporal):
+    for proc in _attn_sites(model, temporal):
+        proc.injection_schedule = injection_schedule
+        proc.inject_background = inject_background
+        proc.variant_schedules = None  # a plain registration is a plain registration (register_variant_schedules)
 
 
 def register_spatial_attention_pnp(model, injection_schedule, inject_background=False):
@@ -78,16 +89,33 @@ def register_temp_attention_pnp(model, injection_schedule, inject_background=Fal
 
 
 def register_resnet_injection(model, injection_schedule):
-    for b in FEATURE_BLOCKS:
-        for i in FEATURE_LAYERS:
-            model.unet.up_blocks[b].resnets[i].injection_schedule = injection_schedule
+    for m in _feature_sites(model, "resnets"):
+        m.injection_schedule, m.variant_schedules = injection_schedule, None
 
 
 def register_temp_conv_injection(model, injection_schedule):
-    for b in FEATURE_BLOCKS:
-        for i in FEATURE_LAYERS:
-            model.unet.up_blocks[b].temp_convs[i].injection_schedule = injection_schedule
+    for m in _feature_sites(model, "temp_convs"):
+        m.injection_schedule, m.variant_schedules = injection_schedule, None
 
 
 def register_out_conv_injection(model, injection_schedule):
-    model.unet.conv_out.injection_schedule = injection_schedule
+    model.unet.conv_out.injection_schedule, model.unet.conv_out.variant_schedules = injection_schedule, None
+
+
+def register_variant_schedules(model, conv=None, spatial=None, temporal=None):
+    """Per-variant injection schedules for a composition of K variants (no counterpart in the reference, whose
+    loop composes one video).  Each argument is None (leave that family as it is) or a list of K entries, one per variant: a
+    schedule in any form the ``register_*`` functions take, or None for the family's shared schedule.  ``conv`` covers the
+    sites of ``register_resnet_injection``, ``register_temp_conv_injection`` and ``register_out_conv_injection``, ``spatial``
+    / ``temporal`` those of the two attention registrations.  Call it AFTER the ``register_*`` functions: each of them resets
+    its sites to the shared schedule."""
+    if conv is not None:
+        sites = list(_feature_sites(model, "resnets")) + list(_feature_sites(model, "temp_convs")) + [model.unet.conv_out]
+        for m in sites:
+            m.variant_schedules = list(conv)
+    if spatial is not None:
+        for proc in _attn_sites(model, False):
+            proc.variant_schedules = list(spatial)
+    if temporal is not None:
+        for proc in _attn_sites(model, True):
+            proc.variant_schedules = list(temporal)

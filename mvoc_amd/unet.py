@@ -137,9 +137,11 @@ class Hookable:
         self.mask = None
         self.injection_schedule = None
         self.inject_background = False
+        # per-variant injection schedules: None, or one entry per variant of the batch -- a schedule in any form
+        # injection_schedule takes, or None for the site's shared injection_schedule (pnp_utils.register_variant_schedules)
+        self.variant_schedules = None
 
-    def injecting(self):
-        s = self.injection_schedule
+    def _on(self, s):
         if s is None or self.t is None:
             return False
         if self.t == 1000:
@@ -147,6 +149,33 @@ class Hookable:
         if isinstance(s, torch.Tensor):
             return bool((s == self.t).any().item()) if s.numel() else False
         return self.t in s
+
+    def injecting(self):
+        if self.variant_schedules is not None:  # any variant
+            return any(self._on(self.injection_schedule if s is None else s) for s in self.variant_schedules)
+        return self._on(self.injection_schedule)
+
+    def injecting_mask(self, nvar):
+        """bit k set = variant k injects at this site now (``injecting()`` on that variant's schedule)"""
+        vs = self.variant_schedules
+        if vs is None:
+            return ((1 << nvar) - 1) if self._on(self.injection_schedule) else 0
+        if len(vs) != nvar:
+            raise RuntimeError(f"{self.site_name()}: variant_schedules holds {len(vs)} schedules, the batch {nvar} variants")
+        return sum(1 << k for k, s in enumerate(vs) if self._on(self.injection_schedule if s is None else s))
+
+    def site_name(self):
+        return getattr(self, "name", None) or type(self).__name__
+
+
+def variant_runs(active, nvar):
+    """the variant axis 0..nvar-1 cut into maximal runs of equal activity: [(k0, k1, injecting)] (paired attention)"""
+    runs, k0 = [], 0
+    for k in range(1, nvar + 1):
+        if k == nvar or ((active >> k) & 1) != ((active >> k0) & 1):
+            runs.append((k0, k, bool((active >> k0) & 1)))
+            k0 = k
+    return runs
 
 
 class Processor(Hookable):
@@ -326,14 +355,34 @@ class Transformer2DModel(_TransformerBase):
         q, k, v = qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:]
         proc = blk.attn1.processor
         ndst = 0
+        active = None
         if proc.injecting() and not eng._pruned:
             ndst, smap = eng.pnp_batch(B, proc.mask)
+            active = eng.site_active(proc)
             masks = eng.device_masks(proc.mask)[1]  # bool masks as {0,1} fp16
             ld = qkv.stride(0)
             ops.pnp_blend_tokens(q, masks, x2=k, frames=F, height=H, width=W, channels=c, chunk_stride=F * hw * ld,
                                  f_stride=hw * ld, p_stride=ld, base_chunk0=proc.inject_background, ndst=ndst, src_map=smap,
-                                 nvar=eng.variants)
-        if ndst == 2 and eng.pair_destinations:
+                                 nvar=eng.variants, active=active)
+        if ndst == 2 and eng.pair_destinations and active is not None:
+            # per-variant schedules: only the variants whose q / k were just overwritten attend with u_k's q, k
+            # equal to c_k's.  Per maximal run of equal activity: an injecting run [k0, k1) is one paired launch (its u and c
+            # blocks still lie K*F*hw rows apart), a non-injecting run plain launches of its u rows and of its c rows
+            a = torch.empty((nimg * hw, c), dtype=H16, device=x.device)
+            nv = eng.variants
+            ns, per = (B - 2 * nv) * F, F * hw
+            s0 = slice(0, ns * hw)
+            ops.flash_attn(q[s0], k[s0], v[s0], nbatch=ns, heads=self.heads, tq=hw, tk=hw, out=a[s0])
+            for k0, k1, on in variant_runs(active, nv):
+                su = slice(ns * hw + k0 * per, ns * hw + k1 * per)
+                sc = slice(ns * hw + (nv + k0) * per, ns * hw + (nv + k1) * per)
+                if on:
+                    ops.flash_attn(q[su], k[su], v[su], nbatch=(k1 - k0) * F, heads=self.heads, tq=hw, tk=hw, out=a[su], v2=v[sc],
+                                   out2=a[sc])
+                else:
+                    for sl in (su, sc):
+                        ops.flash_attn(q[sl], k[sl], v[sl], nbatch=(k1 - k0) * F, heads=self.heads, tq=hw, tk=hw, out=a[sl])
+        elif ndst == 2 and eng.pair_destinations:
             # the injection has just written ONE blended q / k into both destination chunks (pnp_utils.py:664-668): their
             # softmax(q k^T) is the same matrix -- computed once, multiplied into the two chunks' own v (bit-identical outputs)
             a = torch.empty((nimg * hw, c), dtype=H16, device=x.device)
@@ -407,7 +456,7 @@ class TransformerTemporalModel(_TransformerBase):
                 ld = qkv.stride(0)
                 ops.pnp_blend_tokens(q, masks, x2=k, frames=F, height=H, width=W, channels=c, chunk_stride=F * hw * ld,
                                      f_stride=hw * ld, p_stride=ld, base_chunk0=proc.inject_background, ndst=ndst,
-                                     src_map=smap, nvar=eng.variants)
+                                     src_map=smap, nvar=eng.variants, active=eng.site_active(proc))
                 if eng._tail_site is self:  # (prune_source_tail) the last reader of the source chunks was this blend
                     r0 = (B - ndst * eng.variants) * F * hw
                     q, k, v, h, x = q[r0:], k[r0:], v[r0:], h[r0:], x[r0:]
@@ -452,7 +501,7 @@ class ResnetBlock2D(Hookable):
         h = ops.groupnorm(h, *self.norm2, nsample=nimg, rows_per_sample=hw, groups=self.groups, eps=1e-5, silu=True)
         if self.injecting() and not eng._pruned:
             h, _, _ = ops.conv3x3(h, self.conv2_w, self.conv2_b, nimg=nimg, h=H, wd=W, n_store=self.cout)
-            eng.inject_features(h, self.mask, geo, self.cout)
+            eng.inject_features(h, self.mask, geo, self.cout, site=self)
             if self.conv_shortcut is not None:
                 return self.conv_shortcut(x, x2=skip, resid=h, sums=True)
             return ops.add(x, h)
@@ -488,7 +537,7 @@ class TemporalConvLayer(Hookable):
             h = eng.groupnorm5d(h, norm, nsample=B, rows_per_sample=F * hw, groups=self.groups, eps=1e-5, silu=True)
             h = ops.tconv3(h, w, b, nvid=B, frames=F, hw=hw, resid=x if i == 3 else None, sums=True)
         if self.injecting() and not eng._pruned:
-            eng.inject_features(h, self.mask, geo, h.shape[1], full_hw=full_hw)
+            eng.inject_features(h, self.mask, geo, h.shape[1], full_hw=full_hw, site=self)
         return h
 
 
@@ -748,6 +797,17 @@ class I2VGenXLUNet:
                                     torch.cat([rn.time_emb_proj.b[:rn.cout] for rn in rns]))
         self._tall = None
         self._loaded = True
+        # site names for the hook layer's error messages (the reference's module paths)
+        self.conv_out.name, self.conv_in.name = "conv_out", "conv_in"
+        named = [(f"down_blocks.{i}", b) for i, b in enumerate(self.down_blocks)] + [("mid_block", self.mid_block)]
+        named += [(f"up_blocks.{i}", b) for i, b in enumerate(self.up_blocks)]
+        for p, b in named:
+            for kind in ("resnets", "temp_convs"):
+                for j, mod in enumerate(getattr(b, kind)):
+                    mod.name = f"{p}.{kind}.{j}"
+            for kind in ("attentions", "temp_attentions"):
+                for j, tr in enumerate(getattr(b, kind)):
+                    tr.transformer_blocks[0].attn1.processor.name = f"{p}.{kind}.{j}.transformer_blocks.0.attn1.processor"
 
     # ---- PnP helpers ------------------------------------------------------------------------------
     @staticmethod
@@ -837,6 +897,27 @@ class I2VGenXLUNet:
                 sites.append(tr.transformer_blocks[0].attn1.processor)
         return sites
 
+    def site_active(self, site):
+        """the ``active`` argument of an injecting site's blend: None when the site carries no per-variant schedules or every
+        variant injects (the launches of a call without them), else the bitmask of the injecting variants"""
+        if site.variant_schedules is None:
+            return None
+        m = site.injecting_mask(self.variants)
+        return None if m == (1 << self.variants) - 1 else m
+
+    def injection_masks(self, nvar=None):
+        """the per-site injecting_mask() of the CURRENT hook state: what a captured composition step bakes in.  Without
+        per-variant schedules a site's entry is 0 or all ``nvar`` bits, the same partition of steps as ``injection_flags``."""
+        nvar = self.variants if nvar is None else int(nvar)
+        return tuple(s.injecting_mask(nvar) for s in self.hook_sites())
+
+    def check_variant_schedules(self, nvar):
+        """every site's variant_schedules list holds ``nvar`` entries (else an error that names the site)"""
+        for s in self.hook_sites():
+            if s.variant_schedules is not None and len(s.variant_schedules) != nvar:
+                raise RuntimeError(f"{s.site_name()}: variant_schedules holds {len(s.variant_schedules)} schedules, the call "
+                                   f"{nvar} variants")
+
     def injection_flags(self):
         """the per-site injecting() bits of the CURRENT hook state: what a captured iteration bakes in"""
         return tuple(bool(s.injecting()) for s in self.hook_sites())
@@ -857,9 +938,10 @@ class I2VGenXLUNet:
             self._section_mask_cache[key] = m.reshape(m.shape[0], m.shape[1], 1, -1)[..., p0:p1].contiguous()
         return self._section_mask_cache[key]
 
-    def inject_features(self, h, mask_list, geo, channels, full_hw=None):
+    def inject_features(self, h, mask_list, geo, channels, full_hw=None, site=None):
         """feature injection (``pnp_utils.py:970-1004, 1059-1082, 1114-1146``): base = chunk 0, bool mask, no resize.
-        ``full_hw`` is given by temporal sections (see ``section_masks``); elsewhere the rows are whole local frames."""
+        ``full_hw`` is given by temporal sections (see ``section_masks``); elsewhere the rows are whole local frames.
+        ``site``: the calling hook site (its per-variant schedules pick the variants that are written)."""
         B, F, H, W = geo
         ndst, smap = self.pnp_batch(B, mask_list)
         hard = self._all_frame_masks(mask_list)[1]
@@ -870,7 +952,8 @@ class I2VGenXLUNet:
         hard = self.section_masks(mask_list, 1, full_hw) if full_hw is not None else self.device_masks(mask_list)[1]
         ld = h.stride(0)
         ops.pnp_blend_tokens(h, hard, frames=F, height=H, width=W, channels=channels, chunk_stride=F * H * W * ld,
-                             f_stride=H * W * ld, p_stride=ld, base_chunk0=True, ndst=ndst, src_map=smap, nvar=self.variants)
+                             f_stride=H * W * ld, p_stride=ld, base_chunk0=True, ndst=ndst, src_map=smap, nvar=self.variants,
+                             active=None if site is None else self.site_active(site))
         if getattr(h, "chan_sums", None) is not None:
             h.chan_sums = None  # rewritten in place: the producer's GroupNorm statistics no longer describe these rows
 
@@ -1039,7 +1122,7 @@ class I2VGenXLUNet:
         nchw = torch.empty((B * F, C, H, W), dtype=H16, device=self.device)
         nchw[:ns * F] = src.permute(0, 2, 1, 3, 4).reshape(ns * F, C, H, W)
         ops.pnp_blend_nchw(nchw, self.device_masks(co.mask)[1], frames=F, base_chunk0=True, ndst=ndst, src_map=smap,
-                           nvar=self.variants)
+                           nvar=self.variants)  # (taken only when EVERY variant injects at conv_out)
         return nchw.reshape(B, F, C, H, W).permute(0, 2, 1, 3, 4).contiguous()
 
     def spatial_transformers(self):
@@ -1062,7 +1145,9 @@ class I2VGenXLUNet:
         B, C, F, H, W = sample.shape
         hw = H * W
         co = self.conv_out
-        if self.prune_dead_chunks and not self._pruned and self.shard is None and co.injecting():
+        # (per-variant schedules: only when every variant injects at conv_out; a partial mask runs the full batch and the conv_out
+        # blend below overwrites the injecting variants' predictions only -- the reference computes and discards there too)
+        if self.prune_dead_chunks and not self._pruned and self.shard is None and co.injecting() and self.site_active(co) is None:
             return self._forward_source_chunks(sample, timestep, fps, image_latents_first, image_latents, image_embeddings,
                                                encoder_hidden_states, multi_frame_guidance, conditioning)
         self._tail_site = None
@@ -1160,7 +1245,7 @@ class I2VGenXLUNet:
             out = ops.tokens_to_ncfhw(y, B, co.cout, F, H, W)  # [B,C,F,h,w]
             nchw = out.permute(0, 2, 1, 3, 4).reshape(B * F, co.cout, H, W).contiguous()
             ops.pnp_blend_nchw(nchw, self.device_masks(co.mask)[1], frames=F, base_chunk0=True, ndst=ndst, src_map=smap,
-                               nvar=self.variants)
+                               nvar=self.variants, active=self.site_active(co))
             out = nchw.reshape(B, F, co.cout, H, W).permute(0, 2, 1, 3, 4).contiguous()
         else:
             out = ops.tokens_to_ncfhw(y, B, co.cout, F, H, W)

@@ -14,6 +14,8 @@ Used by `bench.py --workload demo`; prints one JSON object.  usage: python tools
 
 --variants K (opt-in): K prompts and seeds over the job's three sources in ONE composition loop (an entry with `variants`,
 DESIGN.md 6i); the JSON line holds the composition-stage time and the mean device time of a step of each kind.
+--variant-thresholds a,b,.. gives variant k its own pnp_spatial_attn_t (the variants' `pnp` key); --sequential
+also runs the K compositions one by one in the same process and reports the ratio.
 
 --shared-source (opt-in): the shape of MVOC's own demo entries, where the background and both objects point at ONE inversion
 directory and the same control frames.  One clip is inverted, then the composition runs with source de-duplication off and then
@@ -319,7 +321,12 @@ class StageTimer:
             e0.record()
             out = step_fn(self, *a, **kw)
             e1.record()
-            timer.steps.append(("conv_out_injection" if self.unet.conv_out.injecting() else "qk", e0, e1))
+            kind = "conv_out_injection" if self.unet.conv_out.injecting() else "qk"
+            proc = self.unet.up_blocks[1].attentions[1].transformer_blocks[0].attn1.processor
+            if proc.variant_schedules is not None:  # per-variant thresholds: how many variants still inject spatial Q/K
+                k = len(proc.variant_schedules)
+                kind += f"_spatial_{bin(proc.injecting_mask(k)).count('1')}of{k}"
+            timer.steps.append((kind, e0, e1))
             return out
 
         P = self.pl.I2VGenXLPipeline
@@ -345,8 +352,10 @@ class StageTimer:
                 "steps_timed": {k: len(v) for k, v in sorted(by.items())}}
 
 
-def run_variants(frames=16, size=512, steps=50, keep=False, variants=2):
-    """K prompts and seeds over the boat_surf-shaped job (three distinct sources), one composition loop (composite.py `variants`)"""
+def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, thresholds=None, sequential=False):
+    """K prompts and seeds over the boat_surf-shaped job (three distinct sources), one composition loop (composite.py `variants`).
+    ``thresholds``: K values of pnp_spatial_attn_t, one per variant (the variants' `pnp` key); ``sequential``: after
+    the one loop, the same K compositions one by one (single entries with the flat threshold) for the comparison."""
     composite, inverse, _ = _import_drivers()
     from mvoc_amd.config import OmegaConf
     from mvoc_amd import pipeline as pl
@@ -369,14 +378,38 @@ def run_variants(frames=16, size=512, steps=50, keep=False, variants=2):
     ct.image_size = [size, size]
     ct.n_frames = frames
     ct.n_steps = steps
-    centry = dict(boat_surf_entry(size), variants=[{"editing_prompt": VARIANT_PROMPTS[k], "seed": 6 + k} for k in range(variants)])
+    if thresholds is not None and len(thresholds) != variants:
+        raise SystemExit(f"--variant-thresholds: {len(thresholds)} values for {variants} variants")
+    var = [{"editing_prompt": VARIANT_PROMPTS[k], "seed": 6 + k} for k in range(variants)]
+    if thresholds is not None:
+        for v, th in zip(var, thresholds):
+            v["pnp"] = {"pnp_spatial_attn_t": float(th)}
+    centry = dict(boat_surf_entry(size), variants=var)
     with StageTimer(pl) as timer:
         composite.main(ct, [centry], dev, synthetic=True)
     res = timer.result()
     out_root = os.path.join(root, "Results", "demo", "i2vgen-xl", "bg_clip", "out")
-    suffix = os.listdir(out_root)[0]
-    dirs = sorted(os.listdir(os.path.join(out_root, suffix)))
-    files = {d: sorted(os.listdir(os.path.join(out_root, suffix, d))) for d in dirs}
+    suffixes = sorted(os.listdir(out_root))  # (per-variant thresholds: every variant under the suffix of its own thresholds)
+    files, where = {}, {}
+    for sfx in suffixes:
+        for d in sorted(os.listdir(os.path.join(out_root, sfx))):
+            files[d], where[d] = sorted(os.listdir(os.path.join(out_root, sfx, d))), sfx
+    dirs = sorted(files)
+    if thresholds is not None:
+        res["variant_thresholds"] = [float(t) for t in thresholds]
+        res["output_suffix_of"] = {d: where[d] for d in dirs}
+    if sequential:  # the K compositions one by one: single entries, the flat threshold key, the same prompts and seeds
+        seq = []
+        for k in range(variants):
+            e = dict(boat_surf_entry(size), edited_video_name=f"seq{k}", **{kk: vv for kk, vv in var[k].items() if kk != "pnp"})
+            if thresholds is not None:
+                e["pnp_spatial_attn_t"] = float(thresholds[k])
+            with StageTimer(pl) as t1:
+                composite.main(ct, [e], dev, synthetic=True)
+            seq.append(t1.result())
+        res["sequential"] = seq
+        res["sequential_composition_s"] = round(sum(r["composition_s"] for r in seq), 3)
+        res["ratio_vs_sequential"] = round(res["composition_s"] / res["sequential_composition_s"], 3)
     if not keep:
         shutil.rmtree(root, ignore_errors=True)
     n_obj = 2
@@ -400,10 +433,15 @@ if __name__ == "__main__":
                     help="one source behind every role: the composition without and with source de-duplication")
     ap.add_argument("--variants", type=int, default=0, metavar="K",
                     help="K prompts and seeds over the job's three sources in one composition loop (composite.py `variants`)")
+    ap.add_argument("--variant-thresholds", type=str, default=None, metavar="a,b,..",
+                    help="with --variants K: K values of pnp_spatial_attn_t, one per variant (the variants' `pnp` key)")
+    ap.add_argument("--sequential", action="store_true",
+                    help="with --variants K: also run the K compositions one by one and report the ratio")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
     if a.variants:
-        print(json.dumps(run_variants(a.frames, a.size, a.steps, a.keep, a.variants)), flush=True)
+        th = None if a.variant_thresholds is None else [float(x) for x in a.variant_thresholds.split(",")]
+        print(json.dumps(run_variants(a.frames, a.size, a.steps, a.keep, a.variants, th, a.sequential)), flush=True)
     else:
         fn = run_shared_source if a.shared_source else run
         print(json.dumps(fn(a.frames, a.size, a.steps, a.keep)), flush=True)
