@@ -1,7 +1,7 @@
-"""Launch census of the headline step (helper module, not collected by pytest).
+"""Launch census of the headline step and of the stages around it: VAE, CLIP towers, mask path (helper module, not collected by pytest).
 
 Three parts:
-  * ``Recorder``: installed as ``mvoc_amd.ops.lib`` for the duration of a recording.  It copies the descriptor (or the scalar and
+  * ``Recorder``: installed as ``lib`` of ``mvoc_amd.ops`` (and of the other modules that hold the library) for the duration of a recording.  It copies the descriptor (or the scalar and
     pointer arguments) of every call of the entry points in ``DESC_ENTRIES`` / ``ARG_ENTRIES``, counts every other ``mvoc_*`` call
     by name, and calls through.  It does no device work and no synchronisation, so it can sit inside a hipGraph capture.
   * ``build_*``: a replay of one recorded call on fresh buffers that the test allocates and fills itself.  Every operand is sized
@@ -39,12 +39,35 @@ ARG_ENTRIES = {
     "mvoc_row_stats_f16": ("x", "stats", "rows", "c", "eps"),
     "mvoc_row_stats_from_moments_f32": ("moments", "rows", "ld", "n", "tile_w", "eps", "out"),
     "mvoc_layernorm_f16": ("x", "gamma", "beta", "out", "rows", "c", "eps"),
+    # stem.hip / norm.hip entries of the VAE, the CLIP towers and the mask path (argument names of include/mvoc_hip.h)
+    "mvoc_conv3x3_small_f16": ("x", "w", "bias", "out", "nimg", "h", "wd", "cin", "cout", "stride", "silu"),
+    "mvoc_conv1x1_small_f16": ("x", "w", "bias", "out", "rows", "cin", "cout"),
+    "mvoc_softmax_rows_f16": ("x", "rows", "cols"),
+    "mvoc_image_to_tokens_f16": ("x", "out", "n", "c", "hw"),
+    "mvoc_tokens_to_image_f16": ("x", "out", "n", "c", "hw", "ld"),
+    "mvoc_gaussian_sample_f16": ("mean", "logvar", "noise", "out", "n"),
+    "mvoc_scale_f16": ("x", "out", "n", "scale"),
+    "mvoc_clip_patches_f16": ("pixels", "out", "nimg", "size", "patch", "kpad"),
+    "mvoc_clip_embed_f16": ("table", "ids", "cls", "pos", "out", "rows", "t", "c"),
+    "mvoc_mask_resize_u8": ("in", "tmp", "out", "n", "H", "W", "h", "w", "bounds_h", "kk_h", "ksize_h", "bounds_v", "kk_v", "ksize_v"),
+    "mvoc_mask_finish": ("v", "float_mask", "bool_mask", "n"),
 }
+STEM_ENTRIES = ("mvoc_conv3x3_small_f16", "mvoc_conv1x1_small_f16", "mvoc_softmax_rows_f16", "mvoc_image_to_tokens_f16",
+                "mvoc_tokens_to_image_f16", "mvoc_gaussian_sample_f16", "mvoc_scale_f16", "mvoc_clip_patches_f16", "mvoc_clip_embed_f16",
+                "mvoc_mask_resize_u8", "mvoc_mask_finish")
 RECORDED = tuple(DESC_ENTRIES) + tuple(n for n in ARG_ENTRIES if n not in DESC_ENTRIES)
 FAMILY = {"mvoc_gemm_f16": "gemm", "mvoc_xs_linear_f16": "xs_linear", "mvoc_flash_attn_f16": "flash_attn",
           "mvoc_temporal_qkv_attn_f16": "tfused", "mvoc_temporal_attn_f16": "temporal_attn", "mvoc_groupnorm_f16": "groupnorm",
           "mvoc_groupnorm_fold_xs_f16": "groupnorm_fold_xs", "mvoc_row_stats_f16": "row_stats",
           "mvoc_row_stats_from_moments_f32": "row_stats_from_moments", "mvoc_layernorm_f16": "layernorm"}
+FAMILY.update({n: n[len("mvoc_"):].replace("_f16", "") for n in STEM_ENTRIES})
+# the modules that hold a reference to the library of their own (`from ._ffi import lib`): the recorder stands in for each of them
+LIB_HOLDERS = ("mvoc_amd.ops", "mvoc_amd.vae", "mvoc_amd.clip", "mvoc_amd._ffi")
+
+# the bounds of the families that are not bit-exact: (rel-L2, max abs) against fp64, those of the per-op tests in test_ops_gpu.py
+FLASH_BOUND = (2e-3, 1e-2)      # test_flash_attn
+GN_BOUND = (2e-3, 1.5e-2)       # test_groupnorm
+LN_BOUND = (1e-3, 1e-2)         # test_layernorm
 
 
 def _is_ptr_type(t):
@@ -103,28 +126,37 @@ class _Proxy:
 
         def call(*args):
             rec.note(name, args)
+            if rec.dry and name in RECORDED:
+                return 0  # descriptor taken, nothing launched
             return fn(*args)
         return call
 
 
 class Recorder:
-    """``rec.install()`` puts the proxy in place of ``mvoc_amd.ops.lib``; ``rec.uninstall()`` (always, in a ``finally``) restores it"""
+    """``rec.install()`` puts the proxy in place of ``lib`` in ``mvoc_amd.ops`` and in the other modules that hold the library
+    (LIB_HOLDERS); ``rec.uninstall()`` (always, in a ``finally``) restores them.  ``dry``: the recorded entries are noted and
+    return 0 without launching (descriptors of extents the caller does not want to run on uninitialised buffers)."""
 
-    def __init__(self):
+    def __init__(self, dry=False):
         self.calls = Counter()      # every mvoc_* call by name
         self.launches = {}          # key -> [Launch, count]
+        self.dry = dry
         self._orig = None
 
     def install(self):
+        import importlib
         from mvoc_amd import ops
         assert self._orig is None and not isinstance(ops.lib, _Proxy), "a recorder is already installed"
-        self._orig = ops.lib
-        ops.lib = _Proxy(self, self._orig)
+        self._orig = {}
+        for name in LIB_HOLDERS:
+            mod = importlib.import_module(name)
+            self._orig[name] = (mod, mod.lib)
+            mod.lib = _Proxy(self, mod.lib)
 
     def uninstall(self):
-        from mvoc_amd import ops
         if self._orig is not None:
-            ops.lib = self._orig
+            for mod, lib in self._orig.values():
+                mod.lib = lib
             self._orig = None
 
     def note(self, name, args):
@@ -376,6 +408,31 @@ def build_gemm(d0, device, seed, workspace_bytes_fn=None):
         bufs["out"].base_alloc.view(torch.int16).fill_(OUT_SENTINEL)
     rewrite(d, bufs)
     return d, bufs, L
+
+
+def apply_image_multipliers(d, bufs, L, mult):
+    """the large-extent pattern: image i of the activation := image 0 times the integer mult[i]; bias (and the logical bias) zero, so
+    that the output of image i is mult[i] times image 0's, exactly (fp32 sums of small integers)"""
+    nimg = len(mult)
+    if d.a2 or d.resid or d.rowadd or d.ln_rowsum or d.act != ACT_NONE or gemm_rows_a(d) % nimg or d.m % nimg:
+        raise RuntimeError("the multiplier pattern is written for single-source launches with a plain epilogue")
+    a = bufs["a"].reshape(nimg, -1)
+    m = torch.tensor(mult, dtype=H16, device=a.device)[:, None]
+    step = 4
+    if mult[0] != 1:
+        raise RuntimeError("image 0 is the unscaled one")
+    for i0 in range(1, nimg, step):
+        a[i0:i0 + step] = a[0:1] * m[i0:i0 + step]
+    if "bias" in bufs:
+        bufs["bias"].zero_()
+    L["bias"] = torch.zeros_like(L["bias"])
+
+
+IMAGE_MULT = (1, -1, 2, -2)  # exact in fp16 and in every fp32 sum; neighbouring images differ, so does every pair less than 4 apart
+
+
+def image_multipliers(nimg):
+    return [IMAGE_MULT[i % 4] for i in range(nimg)]
 
 
 def nearest_index(n_out, n_in, device):
@@ -740,14 +797,24 @@ def chan_sums64(x, rows_per_slab=256):
     return torch.stack([xs.sum(1), (xs * xs).sum(1)], -1)
 
 
-def build_gn(d0, device, seed, fold_args=None):
+def build_gn(d0, device, seed, fold_args=None, mult=None):
+    """``mult`` (the large-extent pattern): sample i := sample 0 times the integer mult[i] (exact in fp16), beta zero; L["x"] then
+    holds sample 0 only"""
     d = copy_desc(d0)
     gen = torch.Generator(device=device).manual_seed(seed)
     rows = d.nsample * d.rows_per_sample
     c2 = d.c - d.c1
     bufs = {"x": alloc(rows * d.c1, H16, d.x % 256, device)}
-    x = (torch.randn(rows, d.c1, generator=gen, device=device) * 2 + 0.5).to(H16)
-    bufs["x"].copy_(x.reshape(-1))
+    if mult is None:
+        x = (torch.randn(rows, d.c1, generator=gen, device=device) * 2 + 0.5).to(H16)
+        bufs["x"].copy_(x.reshape(-1))
+    else:
+        if d.x2 or fold_args is not None or len(mult) != d.nsample or mult[0] != 1:
+            raise RuntimeError("the multiplier pattern is written for a single-source GroupNorm, sample 0 unscaled")
+        x = (torch.randn(d.rows_per_sample, d.c1, generator=gen, device=device) * 2 + 0.5).to(H16)
+        xb = bufs["x"].reshape(d.nsample, -1)
+        for i, s_ in enumerate(mult):
+            torch.mul(x.reshape(-1), s_, out=xb[i])
     L = {"x": x}
     if d.x2:
         bufs["x2"] = alloc(rows * c2, H16, d.x2 % 256, device)
@@ -758,7 +825,7 @@ def build_gn(d0, device, seed, fold_args=None):
                      ("beta", lambda: 0.2 * torch.randn(d.c, generator=gen, device=device))):
         if getattr(d, name):
             bufs[name] = alloc(d.c, H16, getattr(d, name) % 256, device)
-            L[name] = mk().to(H16)
+            L[name] = mk().to(H16) if not (mult is not None and name == "beta") else torch.zeros(d.c, dtype=H16, device=device)
             bufs[name].copy_(L[name])
     if d.out:
         bufs["out"] = alloc(rows * d.c, H16, d.out % 256, device)
@@ -850,9 +917,314 @@ def row_moments64(x, tile_w, ld):
     return out
 
 
+def row_stats_ratio(st, x, eps):
+    """worst deviation of fp32 {mean, rstd} rows from fp64, in units of the bounds of
+    test_gemm_row_moments_and_layernorm_statistics_from_them (mean 1e-4 + 1e-5 |mean|, rstd 2e-5 relative)"""
+    mean, rstd = row_stats64(x, eps)
+    st = st.to(F64)
+    return max(float(((st[:, 0] - mean).abs() / (1e-4 + 1e-5 * mean.abs())).max()), float(((st[:, 1] - rstd).abs() / (2e-5 * rstd)).max()))
+
+
 def rel_l2(a, b):
     a, b = a.to(F64), b.to(F64)
     return float((a - b).norm() / (b.norm() + 1e-300))
+
+
+# ---- the stem entries of the VAE, the CLIP towers and the mask path ------------------------------------------------------------------
+U8, I32 = torch.uint8, torch.int32
+U8_SENTINEL = 0xA5  # the byte the slack around a uint8 output keeps
+
+
+# Bound of the fp32 softmax (norm.hip: softmax_rows_kernel) against fp64, relative to the result p = exp(d) / sum, d = x - max <= 0.
+# Only results that do not round to zero matter: p >= 2^-25 and sum >= 1 give |d| <= 25 ln 2 < 17.4 (below that one fp16 ulp, 2^-24
+# absolute, dwarfs any relative error).  Terms, in units of 2^-23 = one fp32 ulp:
+#   exp(d) as exp2(d * log2 e): the product's rounding and the constant's, |d| log2(e) 2^-24 each, move the result by
+#     2 |d| log2(e) ln(2) 2^-24 = |d| 2^-23 relative, the exponential itself one ulp                              -> 17.4 + 1
+#   the sum: the same error in a p-weighted mean (<= 17.4 + 1), cols / 64 sequential additions per lane and 6 butterfly steps of
+#     half an ulp each                                                                                            -> 18.4 + (cols / 64 + 6) / 2
+#   1 / sum one ulp, the product half an ulp                                                                       -> 1.5
+# (test_stage_census_cpu: test_softmax_bound_derivation measures an fp32 evaluation of the same chain against this.)
+def softmax_rel(cols):
+    return (2 * 18.4 + (cols / 64 + 6) / 2 + 1.5) * 2.0 ** -23
+
+
+# Bound of an fp32 exponential against fp64, relative, at argument h: one ulp for the library routine; where the compiler takes
+# exp2(h * log2 e) instead the argument's rounding adds |h| 2^-23 as above.  (|h| + 2) 2^-23 covers both.
+def exp32_rel(h):
+    return (h.abs() + 2.0) * 2.0 ** -23
+
+
+def stem_extents(name, a):
+    """element counts of every pointer argument of a stem entry: name -> (numel, dtype); what the torch formulation touches"""
+    if name == "mvoc_conv3x3_small_f16":
+        ho, wo = (a["h"] - 1) // a["stride"] + 1, (a["wd"] - 1) // a["stride"] + 1
+        return {"x": (a["nimg"] * a["h"] * a["wd"] * a["cin"], H16), "w": (a["cout"] * 9 * a["cin"], H16), "bias": (a["cout"], H16),
+                "out": (a["nimg"] * ho * wo * a["cout"], H16)}
+    if name == "mvoc_conv1x1_small_f16":
+        return {"x": (a["rows"] * a["cin"], H16), "w": (a["cout"] * a["cin"], H16), "bias": (a["cout"], H16), "out": (a["rows"] * a["cout"], H16)}
+    if name == "mvoc_softmax_rows_f16":
+        return {"x": (a["rows"] * a["cols"], H16)}
+    if name == "mvoc_image_to_tokens_f16":
+        return {"x": (a["n"] * a["c"] * a["hw"], H16), "out": (a["n"] * a["hw"] * a["c"], H16)}
+    if name == "mvoc_tokens_to_image_f16":
+        return {"x": ((a["n"] * a["hw"] - 1) * a["ld"] + a["c"], H16), "out": (a["n"] * a["c"] * a["hw"], H16)}
+    if name == "mvoc_gaussian_sample_f16":
+        return {k: (a["n"], H16) for k in ("mean", "logvar", "noise", "out")}
+    if name == "mvoc_scale_f16":
+        return {"x": (a["n"], H16), "out": (a["n"], H16)}
+    if name == "mvoc_clip_patches_f16":
+        g = a["size"] // a["patch"]
+        return {"pixels": (a["nimg"] * 3 * a["size"] ** 2, H16), "out": (a["nimg"] * g * g * a["kpad"], H16)}
+    if name == "mvoc_clip_embed_f16":
+        nb = a["rows"] // a["t"]
+        return {"table": (STEM_VOCAB * a["c"] if a["ids"] else nb * (a["t"] - 1) * a["c"], H16), "ids": (a["rows"], I32), "cls": (a["c"], H16),
+                "pos": (a["t"] * a["c"], H16), "out": (a["rows"] * a["c"], H16)}
+    if name == "mvoc_mask_resize_u8":
+        return {"in": (a["n"] * a["H"] * a["W"], U8), "tmp": (a["n"] * a["H"] * a["w"], U8), "out": (a["n"] * a["h"] * a["w"], U8),
+                "bounds_h": (a["w"] * 2, I32), "kk_h": (a["w"] * a["ksize_h"], I32), "bounds_v": (a["h"] * 2, I32),
+                "kk_v": (a["h"] * a["ksize_v"], I32)}
+    if name == "mvoc_mask_finish":
+        return {"v": (a["n"], U8), "float_mask": (a["n"], H16), "bool_mask": (a["n"], U8)}
+    raise RuntimeError(f"no replay builder for {name}")
+
+
+STEM_VOCAB = 997  # rows of the replay's token table (the recorded call does not tell the vocabulary's size)
+STEM_OUTPUTS = {"mvoc_conv3x3_small_f16": ("out",), "mvoc_conv1x1_small_f16": ("out",), "mvoc_softmax_rows_f16": ("x",),
+                "mvoc_image_to_tokens_f16": ("out",), "mvoc_tokens_to_image_f16": ("out",), "mvoc_gaussian_sample_f16": ("out",),
+                "mvoc_scale_f16": ("out",), "mvoc_clip_patches_f16": ("out",), "mvoc_clip_embed_f16": ("out",),
+                "mvoc_mask_resize_u8": ("tmp", "out"), "mvoc_mask_finish": ("float_mask", "bool_mask")}
+
+
+def fill_sentinel(t):
+    b = t.base_alloc
+    if b.dtype == H16:
+        b.view(torch.int16).fill_(OUT_SENTINEL)
+    else:
+        b.view(U8).fill_(U8_SENTINEL)
+
+
+def stray_writes(t):
+    """elements of the allocation around the view `t` that no longer hold the sentinel"""
+    b = t.base_alloc
+    off = (t.data_ptr() - b.data_ptr()) // b.element_size()
+    if b.dtype == H16:
+        bb, sv = b.view(torch.int16), OUT_SENTINEL
+    else:
+        bb, sv = b.view(U8).reshape(-1), U8_SENTINEL
+        off, n = off * b.element_size(), t.numel() * b.element_size()
+        return int((bb[:off] != sv).sum()) + int((bb[off + n:] != sv).sum())
+    return int((bb[:off] != sv).sum()) + int((bb[off + t.numel():] != sv).sum())
+
+
+def unwritten(t):
+    """fp16 elements of an output that still hold the sentinel"""
+    return int((t.view(torch.int16) == OUT_SENTINEL).sum())
+
+
+def build_stem(ln, device, seed):
+    """a replay of a recorded stem call: (positional arguments without the stream, buffers by argument name + the logical operands
+    under upper-case names).  Every pointer argument gets a fresh buffer at the recorded address mod 256; an argument the builder
+    does not know fails here, on the host."""
+    from mvoc_amd.unet import pack_conv3x3_small
+    from mvoc_amd.utils import pil_bicubic_tables
+    name, a = ln.name, ln.args
+    gen = torch.Generator(device=device).manual_seed(seed)
+    ext = stem_extents(name, a)
+    T = {}
+    for k, v in a.items():
+        if not isinstance(v, _Ptr):
+            continue
+        if k not in ext:
+            raise RuntimeError(f"replay builder has no buffer for the recorded pointer argument `{k}` ({name})")
+        if v:
+            T[k] = alloc(ext[k][0], ext[k][1], int(v) % 256, device)
+    for k in STEM_OUTPUTS[name]:
+        if k not in T:
+            raise RuntimeError(f"{name}: the recorded call has no `{k}`")
+    if name == "mvoc_conv3x3_small_f16":
+        T["x"].copy_(_ints(T["x"].shape, gen, device, -2, 2))
+        T["W"] = _ints((a["cout"], a["cin"], 3, 3), gen, device, -2, 2)
+        T["w"].copy_(pack_conv3x3_small(T["W"]).reshape(-1))
+        if "bias" in T:
+            T["bias"].copy_(_ints(T["bias"].shape, gen, device, -4, 4))
+    elif name == "mvoc_conv1x1_small_f16":
+        for k, r in (("x", 3), ("w", 3), ("bias", 8)):
+            if k in T:
+                T[k].copy_(_ints(T[k].shape, gen, device, -r, r))
+    elif name == "mvoc_softmax_rows_f16":
+        x = (torch.randn(a["rows"], a["cols"], generator=gen, device=device) * 3).to(H16)
+        x[a["rows"] // 2, a["cols"] // 3] = 40.0  # a dominant score
+        x[0] = x[0, 0]                            # a constant row
+        T["X"] = x
+        fill_sentinel(T["x"])  # (in place: the slack around it is what must stay)
+        T["x"].copy_(x.reshape(-1))
+    elif name in ("mvoc_image_to_tokens_f16", "mvoc_tokens_to_image_f16", "mvoc_clip_patches_f16"):
+        k = "pixels" if name == "mvoc_clip_patches_f16" else "x"
+        T[k].copy_(torch.randn(T[k].shape, generator=gen, device=device).to(H16))
+    elif name == "mvoc_gaussian_sample_f16":
+        for k, sc in (("mean", 1.0), ("logvar", 4.0), ("noise", 1.0)):
+            T[k].copy_((torch.randn(T[k].shape, generator=gen, device=device) * sc).to(H16))
+        edge = torch.tensor([-40.0, 30.0, 0.0, -30.0, 20.0, 19.98, -29.98], device=device).to(H16)[:a["n"]]
+        T["logvar"][:len(edge)] = edge
+    elif name == "mvoc_scale_f16":
+        T["x"].copy_((torch.randn(T["x"].shape, generator=gen, device=device) * 4).to(H16))
+    elif name == "mvoc_clip_embed_f16":
+        for k in ("table", "cls", "pos"):
+            if k in T:
+                T[k].copy_(torch.randn(T[k].shape, generator=gen, device=device).to(H16))
+        if "ids" in T:
+            T["ids"].copy_(torch.randint(0, STEM_VOCAB, T["ids"].shape, generator=gen, device=device, dtype=torch.int32))
+            T["ids"][:2] = torch.tensor([0, STEM_VOCAB - 1], dtype=I32, device=device)[:a["rows"]]
+    elif name == "mvoc_mask_resize_u8":
+        T["in"].copy_(torch.randint(0, 256, T["in"].shape, generator=gen, device=device, dtype=torch.int16).to(U8))
+        bh, kh = pil_bicubic_tables(a["W"], a["w"])
+        bv, kv = pil_bicubic_tables(a["H"], a["h"])
+        if kh.shape[1] != a["ksize_h"] or kv.shape[1] != a["ksize_v"]:
+            raise RuntimeError("the recorded table pitch differs from pil_bicubic_tables of the recorded sizes")
+        for k, t in (("bounds_h", bh), ("kk_h", kh), ("bounds_v", bv), ("kk_v", kv)):
+            T[k].copy_(torch.from_numpy(t).reshape(-1).to(device))
+    elif name == "mvoc_mask_finish":
+        v = torch.randint(0, 256, T["v"].shape, generator=gen, device=device, dtype=torch.int16).to(U8)
+        v[:256] = torch.arange(256, device=device).to(U8)[:a["n"]]  # every value at least once
+        T["v"].copy_(v)
+    for k in STEM_OUTPUTS[name]:
+        if k != "x":
+            fill_sentinel(T[k])
+    args = [T[k].data_ptr() if (isinstance(v, _Ptr) and v) else (None if isinstance(v, _Ptr) else v) for k, v in a.items()]
+    return args, T
+
+
+def pil_resize_u8(frames, w, h):
+    """PIL's Image.resize((w, h)) of "L" images with its default filter (BICUBIC), the path tests/golden/g9_boat_surf_masks.npz was
+    made by (reference utils.py: mask.resize((W // 8, H // 8))): uint8 [n, H, W] -> [n, h, w]"""
+    import numpy as np
+    from PIL import Image
+    return torch.from_numpy(np.stack([np.asarray(Image.fromarray(f).resize((w, h))) for f in frames.cpu().numpy()]))
+
+
+def conv3x3_small64(x, w, bias, stride, silu):
+    """x [n, h, w, cin], logical w [cout, cin, 3, 3] -> (values [n, ho, wo, cout] fp64 after the kernel's roundings, bound)"""
+    xp = torch.nn.functional.pad(x.to(F64), (0, 0, 1, 1, 1, 1))
+    n, h, wd, cin = x.shape
+    ho, wo = (h - 1) // stride + 1, (wd - 1) // stride + 1
+    acc = 0
+    for ky in range(3):
+        for kx in range(3):
+            sl = xp[:, ky:ky + stride * (ho - 1) + 1:stride, kx:kx + stride * (wo - 1) + 1:stride]
+            acc = acc + sl.reshape(-1, cin) @ w[:, :, ky, kx].to(F64).t()
+    v = r16(acc + (bias.to(F64) if bias is not None else 0))
+    bound = torch.zeros_like(v)
+    if silu:
+        a64 = silu64(v)
+        v, bound = r16(a64), ulp16(a64)
+    return v.reshape(n, ho, wo, -1), bound.reshape(n, ho, wo, -1)
+
+
+def softmax64(x):
+    """softmax of the fp16 input in fp64, rounded once -> (values, alternatives).  The kernel rounds an fp32 value within
+    softmax_rel(cols) of p: where that error reaches across an fp16 rounding boundary the neighbouring value is accepted, nothing else
+    (never more than one fp16 ulp of the result plus the fp32 evaluation error, and far tighter away from the boundaries)"""
+    p = torch.softmax(x.to(F64), -1)
+    tol = softmax_rel(x.shape[-1]) * p
+    return r16(p), (r16(p - tol), r16(p + tol))
+
+
+def gaussian_sample64(mean, logvar, noise):
+    """DiagonalGaussianDistribution.sample() with a rounding at each eager op (stem.hip: gaussian_sample_kernel):
+    out = r16(mean + r16(r16(exp(r16(0.5 * clamp(logvar, -30, 20)))) * noise)).  Returns (values, alternatives): where the fp32
+    exponential's error (exp32_rel) reaches across a rounding boundary of r16(exp(.)) the kernel may hold the neighbouring fp16
+    value of the standard deviation; `alternatives` are the chain's results with that neighbour (equal to `values` elsewhere)"""
+    mean, noise = mean.to(F64), noise.to(F64)
+    h = r16(0.5 * logvar.to(F64).clamp(-30.0, 20.0))
+    e = torch.exp(h)
+    sd = r16(e)
+    chain = lambda s: r16(mean + r16(s * noise))
+    out = chain(sd)
+    tol = exp32_rel(h) * e
+    lo, hi = r16(e - tol), r16(e + tol)
+    return out, (torch.where(lo != sd, chain(lo), out), torch.where(hi != sd, chain(hi), out))
+
+
+def scale64(x, scale):
+    """python float times an fp16 tensor: the fp32 product of float(scale) and x rounded to fp32, then to fp16"""
+    s32 = torch.tensor(scale, dtype=F32).to(F64)
+    return (x.to(F64) * s32).to(F32).to(H16)
+
+
+def clip_patches_ref(x, patch, kpad):
+    """[n, 3, size, size] -> im2col rows [n * g * g, kpad], k = (c, py, px), zero columns past 3 * patch^2"""
+    n, c, size, _ = x.shape
+    g = size // patch
+    rows = x.reshape(n, c, g, patch, g, patch).permute(0, 2, 4, 1, 3, 5).reshape(n * g * g, c * patch * patch)
+    return torch.nn.functional.pad(rows, (0, kpad - rows.shape[1]))
+
+
+def clip_embed_ref(table, ids, cls, pos, rows, t):
+    """out[row] = src(row) + pos[row % t], rounded once; src = table[ids[row]], or the class row at t == 0 and patch row
+    (row / t) * (t - 1) + row % t - 1 otherwise"""
+    c = pos.shape[1]
+    r = torch.arange(rows, device=pos.device)
+    if ids is not None:
+        src = table[ids.long()]
+    else:
+        src = torch.cat([cls.reshape(1, 1, c).expand(rows // t, 1, c), table.reshape(rows // t, t - 1, c)], 1).reshape(rows, c)
+    return (src.to(F64) + pos[r % t].to(F64)).to(H16)
+
+
+def stem_ref(ln, T):
+    """float64 (or exact) restatement of a stem entry on the replay's buffers: output name -> (values, bound or None = bit for bit)"""
+    name, a = ln.name, ln.args
+    if name == "mvoc_conv3x3_small_f16":
+        v, b = conv3x3_small64(T["x"].reshape(a["nimg"], a["h"], a["wd"], a["cin"]), T["W"], T.get("bias"), a["stride"], a["silu"])
+        return {"out": (v.reshape(-1), b.reshape(-1) if a["silu"] else None)}
+    if name == "mvoc_conv1x1_small_f16":
+        y = T["x"].reshape(a["rows"], a["cin"]).to(F64) @ T["w"].reshape(a["cout"], a["cin"]).to(F64).t()
+        return {"out": (r16(y + (T["bias"].to(F64) if "bias" in T else 0)).reshape(-1), None)}
+    if name == "mvoc_softmax_rows_f16":
+        v, (lo, hi) = softmax64(T["X"])
+        return {"x": (v.reshape(-1), (lo.reshape(-1), hi.reshape(-1)))}
+    if name == "mvoc_image_to_tokens_f16":
+        return {"out": (T["x"].reshape(a["n"], a["c"], a["hw"]).permute(0, 2, 1).reshape(-1), None)}
+    if name == "mvoc_tokens_to_image_f16":
+        x = T["x"].as_strided((a["n"], a["hw"], a["c"]), (a["hw"] * a["ld"], a["ld"], 1), T["x"].storage_offset())
+        return {"out": (x.permute(0, 2, 1).reshape(-1), None)}
+    if name == "mvoc_gaussian_sample_f16":
+        v, alts = gaussian_sample64(T["mean"], T["logvar"], T["noise"])
+        return {"out": (v, alts)}
+    if name == "mvoc_scale_f16":
+        return {"out": (scale64(T["x"], a["scale"]), None)}
+    if name == "mvoc_clip_patches_f16":
+        return {"out": (clip_patches_ref(T["pixels"].reshape(a["nimg"], 3, a["size"], a["size"]), a["patch"], a["kpad"]).reshape(-1), None)}
+    if name == "mvoc_clip_embed_f16":
+        c = a["c"]
+        return {"out": (clip_embed_ref(T["table"].reshape(-1, c), T.get("ids"), T.get("cls"), T["pos"].reshape(-1, c), a["rows"], a["t"]).reshape(-1), None)}
+    if name == "mvoc_mask_resize_u8":
+        fr = T["in"].reshape(a["n"], a["H"], a["W"])
+        return {"tmp": (pil_resize_u8(fr, a["w"], a["H"]).reshape(-1).to(fr.device), None),
+                "out": (pil_resize_u8(fr, a["w"], a["h"]).reshape(-1).to(fr.device), None)}
+    if name == "mvoc_mask_finish":
+        v = T["v"]
+        return {"float_mask": ((v.to(F64) / 255.0).to(F32).to(H16), None), "bool_mask": ((v > 10).to(U8), None)}
+    raise RuntimeError(f"no reference for {name}")
+
+
+def stem_compare(ln, T):
+    """(number of wrong elements, worst deviation in units of the bound: 0 for the bit-exact outputs, number of elements that hold an
+    accepted alternative) of a replayed stem call"""
+    bad, worst, alt = 0, 0.0, 0
+    for k, (ref, bound) in stem_ref(ln, T).items():
+        got = T[k]
+        if bound is None:
+            bad += int((got.view(torch.int16) != ref.to(got.dtype).view(torch.int16)).sum()) if got.dtype == H16 else int((got != ref).sum())
+        elif isinstance(bound, tuple):
+            g = got.to(F64)
+            bad += int(((g != ref) & (g != bound[0]) & (g != bound[1])).sum())
+            alt += int(((g != ref) & ((g == bound[0]) | (g == bound[1]))).sum())
+        else:
+            dev = (got.to(F64) - ref).abs()
+            bad += int((~(dev <= bound)).sum())
+            worst = max(worst, float((dev / bound).nan_to_num(1e9).max()))
+    return bad, worst, alt
 
 
 def describe(ln):
