@@ -9,7 +9,8 @@ keys, hook registration order and output naming as the reference's ``i2vgen-xl/c
 ``--dedup_sources``: roles (background, objects) that are the same source share one UNet chunk.
 An entry with ``variants: [{...}, ...]`` composes K prompts / seeds / guidance scales over its sources in one loop
 (``merge_variants``; files under ``.../variant_00/``, ``variant_01/`` ...); a variant's ``pnp: {...}`` gives it injection
-thresholds of its own.
+thresholds of its own.  An entry's ``obj_offset: [[dx, dy], ...]`` (one item per object: a pair, or one pair per frame; image
+pixels in multiples of 8) places the objects at composition time (``placement_kwargs``; shared by the entry's variants).
 """
 import argparse
 import json
@@ -129,6 +130,16 @@ def merge_variants(template_config, entry):
     return config, merged
 
 
+def placement_kwargs(config):
+    """the entry's optional ``obj_offset`` -> keyword arguments of the sampling call: none when the key is absent (the call is
+    then exactly today's), else ``obj_offsets`` = one item per object, ``[dx, dy]`` or one such pair per frame, in image pixels
+    (the call checks and normalises them).  Shared by the variants of an entry: not one of ``VARIANT_KEYS``."""
+    if "obj_offset" not in config or config.obj_offset is None:
+        return {}
+    plain = lambda v: [plain(x) for x in v] if hasattr(v, "__iter__") and not isinstance(v, (str, bytes)) else v
+    return {"obj_offsets": plain(config.obj_offset)}
+
+
 def variant_output_dir(config, k):
     """``<output_dir>/<output_suffix of the variant's merged config>/variant_{k:02d}``"""
     return os.path.join(config.output_dir, output_suffix(config), f"variant_{k:02d}")
@@ -174,7 +185,8 @@ def main(template_config, configs_list, device, synthetic=False, dedup_sources=F
                   random_noise_ratio=config.random_noise_ratio, bg_inv_latents_path=config.bg_ddim_latents_path,
                   obj_ddim_latents_path=config.obj_ddim_latents_path,
                   obj_ddim_latents_idx_offset=config.obj_ddim_latents_idx_offset,
-                  obj_random_noise_fusion=config.obj_random_noise_fusion, fusion_steps=config.fusion_step)
+                  obj_random_noise_fusion=config.obj_random_noise_fusion, fusion_steps=config.fusion_step,
+                  **placement_kwargs(config))
         if variants is None:
             output_dirs, configs = [os.path.join(config.output_dir, output_suffix(config))], [config]
         else:  # K variants in one loop: per-variant prompt / negative prompt / seed / cfg / main image, everything else shared

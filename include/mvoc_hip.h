@@ -328,6 +328,30 @@ int mvoc_pnp_blend_scatter_tokens_variants_sel(const mvoc_pnp_desc* d, int32_t n
                                                uint32_t active, void* stream);
 int mvoc_pnp_blend_scatter_nchw_variants_sel(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
                                              uint32_t active, void* stream);
+/* Placement: the _variants_sel entries with a per-frame integer translation of every object -- here nvar = 1 and
+ * every bit of `active` set are allowed too.  `place` is a DEVICE table of int32 pairs [nobj][frames][2] = (dfy, dfx), the
+ * feature offsets of object j in frame f on THIS call's height x width grid; the caller owns it and keeps it unchanged for as
+ * long as a captured graph may replay the launch.  For destination pixel (py, px) of frame f object j contributes the vector of
+ * its chunk at pixel (py - dfy, px - dfx) of frame f and the mask value masks[j][f][nearest(py)][nearest(px)] -- the masks are
+ * given in DESTINATION coordinates (mvoc_shift_planes_f16 moves them there) and sampled at the destination pixel as above.
+ * Where the source pixel lies outside the frame the object is absent: value 0 and mask 0 enter the same three fp16-rounded ops
+ * (nothing is skipped: a -0.0 base becomes +0.0 as under a zero mask).  The destination rows are bit-identical to the entries
+ * above on object chunks shifted with zero fill and masks zeroed where the source is out of range; a table of zeros is the
+ * _variants_sel entry.  Same traffic as _variants_sel.  Every int32 offset is valid (an object may leave the frame entirely);
+ * the table's contents are on the device and are not read by the host.
+ * Requires a non-NULL table, 1 <= nvar <= 8, 1 <= active < (1u << nvar) and a valid map (else -1 and an error text, nothing
+ * written). */
+int mvoc_pnp_blend_scatter_tokens_placed(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
+                                         uint32_t active, const int32_t* place, void* stream);
+int mvoc_pnp_blend_scatter_nchw_placed(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
+                                       uint32_t active, const int32_t* place, void* stream);
+/* Zero-filled per-frame integer translation of contiguous fp16 planes [nplane][frames][h][w] (src != dst):
+ *     dst[pl][f][y][x] = src[pl][f][y - dy_f][x - dx_f], or 0 where that pixel lies outside the plane
+ * `offsets`: DEVICE int32 pairs [frames][2] = (dy_f, dx_f), shared by the nplane planes -- the planes of one call belong to one
+ * object: one [F][h][w] mask of a [nobj, F, h, w] stack per call (nplane = 1), or the four channels of an object's
+ * [4, F, h, w] latents (nplane = 4).  Every int32 offset is valid. */
+int mvoc_shift_planes_f16(const void* src, void* dst, int32_t nplane, int32_t frames, int32_t h, int32_t w,
+                          const int32_t* offsets, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Loop glue on [B,4,F,h,w] fp16 latents, BIT-EXACT vs the reference's eager fp16 op chain.

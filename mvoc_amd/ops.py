@@ -14,7 +14,7 @@ from ._ffi import (A_CONV3X3, A_PLAIN, A_TEMPORAL3, ACT_GEGLU, ACT_GELU, ACT_NON
                    PnpDesc, TAttnDesc, TFusedDesc, XsDesc, check, lib)
 
 __all__ = ["linear", "conv3x3", "tconv3", "flash_attn", "temporal_attn", "groupnorm", "groupnorm_moments", "groupnorm_apply_moments", "layernorm", "pnp_blend_tokens",
-           "pnp_blend_nchw", "ddim_step", "latent_fusion", "timestep_embedding", "act", "add", "conv3x3_small",
+           "pnp_blend_nchw", "level_offset", "level_offsets", "place_table", "shift_planes", "ddim_step", "latent_fusion", "timestep_embedding", "act", "add", "conv3x3_small",
            "adaptive_avgpool", "ncfhw_to_tokens", "tokens_to_ncfhw", "temporal_encoder4", "conv1x1_small", "softmax_rows", "ACT_NONE", "ACT_GEGLU",
            "ACT_SILU", "ACT_GELU"]
 
@@ -543,19 +543,26 @@ def _active_mask(active, nvar, what):
 
 
 def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride, f_stride, p_stride, x2=None,
-                     base_chunk0=False, ndst=2, src_map=None, nvar=1, active=None):
+                     base_chunk0=False, ndst=2, src_map=None, nvar=1, active=None, place=None):
     """In-place masked blend + scatter on channel-contiguous data (see include/mvoc_hip.h).  ``ndst``: trailing
     destination chunks (2 = [uncond, cond], 1 = [cond] with CFG off).  ``src_map`` = (nsrc, obj_chunks): the batch holds
     nsrc de-duplicated source chunks, object j reads chunk obj_chunks[j] (None: [bg, obj_1..obj_n], the unmapped entry).
     ``nvar`` = K > 1: K variants share the sources, the batch is [s.., u_1..u_K, c_1..c_K] ([s.., c_1..c_K] with ndst 1).
-    ``active``: bit k set = variant k injects (None or all K bits: every variant, the entries of a call without it)."""
+    ``active``: bit k set = variant k injects (None or all K bits: every variant, the entries of a call without it).
+    ``place``: the table of ``place_table`` for this height x width: every object is read at its shifted pixel,
+    ``masks`` are in destination coordinates -- the ``_placed`` entry, whatever ``nvar`` / ``src_map`` / ``active`` are."""
     d = _pnp_desc(x, x2, masks, chunk_stride, f_stride, p_stride, frames, height, width, channels, base_chunk0, ndst)
     active = _active_mask(active, nvar, "pnp_blend_tokens")
-    if nvar != 1:
+    if nvar != 1 or place is not None:
         nsrc, chunks = _variant_map(src_map, d.nobj)
         last = (nsrc + (int(ndst) or 2) * int(nvar) - 1) * chunk_stride
         _check_variants(x, x2, nvar, last + (frames - 1) * f_stride + (height * width - 1) * p_stride + channels,
                         "pnp_blend_tokens")
+        if place is not None:
+            _check_place(place, d.nobj, frames, "pnp_blend_tokens")
+            check(lib.mvoc_pnp_blend_scatter_tokens_placed(C.byref(d), nsrc, chunks, int(nvar), _all_or(active, nvar),
+                                                           place.data_ptr(), _stream()), "pnp_blend_scatter_tokens_placed")
+            return x
         if active is not None:
             check(lib.mvoc_pnp_blend_scatter_tokens_variants_sel(C.byref(d), nsrc, chunks, int(nvar), active, _stream()),
                   "pnp_blend_scatter_tokens_variants_sel")
@@ -570,17 +577,22 @@ def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride,
     return x
 
 
-def pnp_blend_nchw(x, masks, *, frames, x2=None, base_chunk0=True, ndst=2, src_map=None, nvar=1, active=None):
+def pnp_blend_nchw(x, masks, *, frames, x2=None, base_chunk0=True, ndst=2, src_map=None, nvar=1, active=None, place=None):
     """In-place on x [(nobj+1+ndst)*F, C, H, W] (reference feature-map layout); with ``src_map`` = (nsrc, obj_chunks)
     x is [(nsrc+ndst)*F, C, H, W], with ``nvar`` = K > 1 [(nsrc+ndst*K)*F, C, H, W]; ``active`` picks the variants that are
-    written (see ``pnp_blend_tokens``)."""
+    written, ``place`` moves the objects (see ``pnp_blend_tokens``)."""
     if x.dim() != 4 or not x.is_contiguous():
         raise RuntimeError("pnp_blend_nchw: x must be contiguous [N, C, H, W]")
     d = _pnp_desc(x, x2, masks, 0, 0, 0, frames, x.shape[2], x.shape[3], x.shape[1], base_chunk0, ndst)
     active = _active_mask(active, nvar, "pnp_blend_nchw")
-    if nvar != 1:
+    if nvar != 1 or place is not None:
         nsrc, chunks = _variant_map(src_map, d.nobj)
         _check_variants(x, x2, nvar, (nsrc + (int(ndst) or 2) * int(nvar)) * frames * x[0].numel(), "pnp_blend_nchw")
+        if place is not None:
+            _check_place(place, d.nobj, frames, "pnp_blend_nchw")
+            check(lib.mvoc_pnp_blend_scatter_nchw_placed(C.byref(d), nsrc, chunks, int(nvar), _all_or(active, nvar),
+                                                         place.data_ptr(), _stream()), "pnp_blend_scatter_nchw_placed")
+            return x
         if active is not None:
             check(lib.mvoc_pnp_blend_scatter_nchw_variants_sel(C.byref(d), nsrc, chunks, int(nvar), active, _stream()),
                   "pnp_blend_scatter_nchw_variants_sel")
@@ -593,6 +605,63 @@ def pnp_blend_nchw(x, masks, *, frames, x2=None, base_chunk0=True, ndst=2, src_m
         nsrc, chunks = _src_map_args(src_map, d.nobj)
         check(lib.mvoc_pnp_blend_scatter_nchw_mapped(C.byref(d), nsrc, chunks, _stream()), "pnp_blend_scatter_nchw_mapped")
     return x
+
+
+# ---- placement: per-frame integer translation of the objects ------------------------------------------
+def level_offset(d, size, mask_size):
+    """the offset ``d`` (latent grid, ``mask_size`` rows or columns) on a feature grid of ``size``: round-half-up of
+    d * size / mask_size in integers, floor division for negatives"""
+    d, size, mask_size = int(d), int(size), int(mask_size)
+    return (2 * d * size + mask_size) // (2 * mask_size)
+
+
+def level_offsets(placement, height, width, mask_h, mask_w):
+    """``placement`` = per object, per frame (dy, dx) on the mask_h x mask_w latent grid -> the same structure of (dfy, dfx)
+    on a height x width feature grid (``level_offset`` per axis)"""
+    return tuple(tuple((level_offset(dy, height, mask_h), level_offset(dx, width, mask_w)) for dy, dx in obj) for obj in placement)
+
+
+def place_table(placement, height, width, mask_h, mask_w, device):
+    """the device table the ``_placed`` blend entries read: int32 [nobj, F, 2] = (dfy, dfx) of ``level_offsets``.  An offset that
+    does not fit int32 is refused here (the library cannot see the table's contents); every int32 value is valid to the kernels"""
+    lv = level_offsets(placement, height, width, mask_h, mask_w)
+    if len({len(o) for o in lv}) != 1 or not lv or not lv[0]:
+        raise RuntimeError("place_table: every object needs the same number (>= 1) of per-frame offsets")
+    for j, obj in enumerate(lv):
+        for f, pair in enumerate(obj):
+            if any(not -2 ** 31 <= v < 2 ** 31 for v in pair):
+                raise RuntimeError(f"place_table: offset {pair} of object {j}, frame {f} does not fit int32")
+    return torch.tensor(lv, dtype=torch.int32).to(device).contiguous()
+
+
+def _check_place(place, nobj, frames, what):
+    _chk(place, "place", torch.int32)
+    if tuple(place.shape) != (nobj, frames, 2) or not place.is_contiguous():
+        raise RuntimeError(f"{what}: place must be a contiguous int32 [nobj = {nobj}, F = {frames}, 2] table, got {tuple(place.shape)}")
+
+
+def _all_or(active, nvar):
+    """the ``_placed`` entries take the bitmask in every case: all bits for 'every variant injects'"""
+    return (1 << int(nvar)) - 1 if active is None else active
+
+
+def shift_planes(src, offsets, out=None):
+    """zero-filled per-frame integer translation of contiguous fp16 planes [..., F, h, w] (leading dims = planes of ONE
+    object): out[.., f, y, x] = src[.., f, y - dy_f, x - dx_f] or 0.  ``offsets``: device int32 [F, 2] = (dy_f, dx_f)."""
+    _chk(src, "src"), _chk(offsets, "offsets", torch.int32)
+    if src.dim() < 3 or not src.is_contiguous():
+        raise RuntimeError(f"shift_planes: src must be contiguous [..., F, h, w], got {tuple(src.shape)}")
+    frames, h, w = src.shape[-3:]
+    if tuple(offsets.shape) != (frames, 2) or not offsets.is_contiguous():
+        raise RuntimeError(f"shift_planes: offsets must be a contiguous int32 [F = {frames}, 2] table, got {tuple(offsets.shape)}")
+    if out is None:
+        out = torch.empty_like(src)
+    _chk(out, "out")
+    if out.shape != src.shape or not out.is_contiguous():
+        raise RuntimeError("shift_planes: out must be contiguous and of src's shape")
+    check(lib.mvoc_shift_planes_f16(src.data_ptr(), out.data_ptr(), src.numel() // (frames * h * w), frames, h, w, offsets.data_ptr(),
+                                    _stream()), "shift_planes")
+    return out
 
 
 def ddim_step(x, v_cond, coef_dev, v_uncond=None, out=None):

@@ -182,6 +182,39 @@ def variant_layout(n_obj, nvar=1, do_cfg=True, smap=None):
     return dict(nsrc=nsrc, nb=nsrc + ndst * nvar, src=[0] + list(chunks), obj_chunks=chunks, u=u, c=c, ndst=ndst)
 
 
+def normalize_obj_offsets(obj_offsets, n_obj, num_frames, factor=8):
+    """``obj_offsets`` of the sampling call -> the placement the engine takes, or None.  One entry per object:
+    ``(dx, dy)`` for every frame, or a list of ``num_frames`` pairs (a path), in image pixels; each a multiple of the VAE
+    factor (the latent grid is 1 / ``factor`` of the image).  -> None when there is nothing to move (no argument, or all
+    zeros: the call is then exactly a call without it), else a hashable tuple, per object a tuple of ``num_frames`` pairs
+    ``(dy, dx)`` on the latent grid.  Anything else is a ValueError that names the object."""
+    if obj_offsets is None:
+        return None
+    objs = list(obj_offsets)
+    if len(objs) != n_obj:
+        raise ValueError(f"obj_offsets: {len(objs)} entries for {n_obj} objects (one per object)")
+    is_int = lambda v: isinstance(v, int) and not isinstance(v, bool)
+    out = []
+    for j, entry in enumerate(objs):
+        entry = list(entry) if isinstance(entry, (list, tuple)) else entry
+        if isinstance(entry, list) and len(entry) == 2 and all(is_int(v) for v in entry):
+            pairs = [entry] * num_frames
+        elif isinstance(entry, list) and all(isinstance(q, (list, tuple)) and len(q) == 2 and all(is_int(v) for v in q) for q in entry):
+            if len(entry) != num_frames:
+                raise ValueError(f"obj_offsets: object {j} has {len(entry)} per-frame offsets, the clip {num_frames} frames")
+            pairs = entry
+        else:
+            raise ValueError(f"obj_offsets: object {j} needs (dx, dy) or {num_frames} (dx, dy) pairs of integers, got {entry!r}")
+        for f, (dx, dy) in enumerate(pairs):
+            if dx % factor or dy % factor:
+                raise ValueError(f"obj_offsets: object {j}, frame {f}: ({dx}, {dy}) is not a multiple of {factor} image pixels "
+                                 "(placements are integer translations on the latent grid)")
+        out.append(tuple((int(dy) // factor, int(dx) // factor) for dx, dy in pairs))
+    if all(v == 0 for obj in out for pair in obj for v in pair):
+        return None
+    return tuple(out)
+
+
 def crosses_gemm_offset_line(nb, frames, h, w, width0):
     """the eight-phase GEMM tiles address their operands with 32-bit byte offsets (gemm.hip g8_ok): the widest level-0 tensor
     of a forward, the feed-forward's [nb * F * h * w, 4 * width0] fp16, must stay under 2 GB for them to be chosen"""
@@ -559,7 +592,25 @@ class I2VGenXLPipeline:
         return tensor2vid(self.conditioner.decode(latents), output_type)
 
     # ---- composition --------------------------------------------------------------------------------------
-    def make_composition_state(self, latents, cond, masks, guidance_scale, dedup_sources=None, variants=1):
+    def place_masks(self, masks, placement):
+        """the call's masks moved to destination coordinates: per object the soft and the hard mask shifted by
+        the object's per-frame offsets with zero fill (``ops.shift_planes``) -> (masks in the form they came in, the device
+        table int32 [nobj, F, 2] of the latent-grid offsets)"""
+        if len(placement) != len(masks):
+            raise ValueError(f"placement: offsets for {len(placement)} objects, {len(masks)} masks")
+        dev = self.device
+        frames = masks[0][0].shape[-3]
+        if any(len(obj) != frames for obj in placement):
+            raise ValueError(f"placement: every object needs {frames} per-frame offsets")
+        table = torch.tensor(placement, dtype=torch.int32).to(dev).contiguous()
+        moved = []
+        for j, (soft, hard) in enumerate(masks):
+            s16 = ops.shift_planes(soft.to(dev, H16).contiguous(), table[j])
+            h16 = ops.shift_planes(hard.to(dev, H16).contiguous(), table[j])
+            moved.append((s16.to(soft.dtype), h16.to(hard.dtype)))
+        return moved, table
+
+    def make_composition_state(self, latents, cond, masks, guidance_scale, dedup_sources=None, variants=1, placement=None):
         """static buffers + the captured iteration variants of the composition loop.
         cond: dict(encoder_hidden_states [n,77,D], image_embeddings [n,F,D], image_latents_first, image_latents, fps).
         The state keeps its OWN copy of ``cond``: the hoisted conditioning (``prepare_conditioning``) and the shared-CFG-prefix
@@ -568,8 +619,16 @@ class I2VGenXLPipeline:
         ``dedup_sources`` (None: ``self.dedup_sources``): classify the source roles once (``source_classes``); every step then
         runs the batch its source map (``plan_source_map``) lays out, each map with its own buffers, built on first use.
         ``variants`` = K > 1: ``latents`` is [K, 4, F, h, w], ``cond`` rows follow ``variant_layout`` ([bg, obj.., u_1..u_K,
-        c_1..c_K]), ``guidance_scale`` is a float or K floats (all > 1 or none), a step's coefficient rows are [K, 5]."""
+        c_1..c_K]), ``guidance_scale`` is a float or K floats (all > 1 or none), a step's coefficient rows are [K, 5].
+        ``placement`` (``normalize_obj_offsets``; None: objects stay where they are): ``masks`` come in the objects' source
+        coordinates and are moved ONCE, here, to destination coordinates -- the state's masks everywhere (hooks, fusion)."""
         cond = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in cond.items()}
+        place_dev = None
+        if placement is not None:
+            if self.unet.shard is not None:
+                raise RuntimeError("a placement does not combine with the frame shard: the section masks are cut to pixel slabs "
+                                   "and a shift crosses slabs")
+            masks, place_dev = self.place_masks(masks, placement)
         n_obj = len(masks)
         nvar = int(variants)
         scales = [float(g) for g in guidance_scale] if isinstance(guidance_scale, (list, tuple)) else [float(guidance_scale)]
@@ -589,7 +648,8 @@ class I2VGenXLPipeline:
               "coef": torch.zeros(5 if nvar == 1 else (nvar, 5), dtype=torch.float32, device=dev),
               "masks": masks, "variants": {}, "cond": cond, "n_obj": n_obj, "nvar": nvar,
               "fusion_masks": torch.stack([m[0].to(dev, H16) for m in masks]).contiguous(),
-              "fusion_objs": torch.empty((n_obj, 1) + tuple(latents.shape[1:]), dtype=H16, device=dev), "maps": {}}
+              "fusion_objs": torch.empty((n_obj, 1) + tuple(latents.shape[1:]), dtype=H16, device=dev), "maps": {},
+              "placement": placement, "place_dev": place_dev, "place_tables": []}
         st["build_map"] = lambda smap: self._composition_batch(st, smap, do_cfg)
         st["maps"][None] = st["build_map"](None)
 
@@ -632,12 +692,18 @@ class I2VGenXLPipeline:
             saved_sp, u.shared_prefix_chunks = u.shared_prefix_chunks, (2 if st["share_cfg_prefix"] else 0)
             saved_sc, u.source_chunks = u.source_chunks, smap
             saved_nv, u.variants = u.variants, nvar
+            saved_pl, u.placement = u.placement, st["placement"]
             try:
                 noise = u.forward_ext(inp, st["t"], mcond["fps"], mcond["image_latents_first"], mcond["image_latents"],
                                       mcond["image_embeddings"], mcond["encoder_hidden_states"], multi_frame_guidance=False,
                                       conditioning=prepared)[0]
             finally:
                 u.prune_source_tail, u.shared_prefix_chunks, u.source_chunks, u.variants = saved, saved_sp, saved_sc, saved_nv
+                u.placement = saved_pl
+            # the engine's per-level offset tables are read by this state's captured graphs: they live as long as the state,
+            # also after the engine drops its cache for another placement
+            if st["placement"] is not None and not any(d is u._place_cache[1] for d in st["place_tables"]):
+                st["place_tables"].append(u._place_cache[1])
             ops.ddim_step(x, noise[nb - nvar:nb].contiguous(), st["coef"],
                           v_uncond=noise[nb - 2 * nvar:nb - nvar].contiguous() if do_cfg else None, out=x)
 
@@ -650,7 +716,10 @@ class I2VGenXLPipeline:
         if fuse is not None:
             mix, rnf, fobjs = fuse
             for j, o in enumerate(fobjs):
-                st["fusion_objs"][j].copy_(o)
+                if st["place_dev"] is None:
+                    st["fusion_objs"][j].copy_(o)
+                else:  # the object's inverted latents move with it (zero fill; the fusion masks are the shifted ones)
+                    ops.shift_planes(o.to(self.device, H16).contiguous(), st["place_dev"][j], out=st["fusion_objs"][j])
             ops.latent_fusion(st["latents"], bg_latents, st["fusion_objs"], st["fusion_masks"], mix, rnf, out=st["latents"],
                               nvar=st["nvar"])
             obj_latents = fobjs
@@ -672,7 +741,8 @@ class I2VGenXLPipeline:
         # without them), the device copies of the masks and the batch's source map: all are part of the variant key
         u = self.unet
         vkey = (u.injection_masks(st["nvar"]), u.mask_key(st["masks"]), bool(u.pair_destinations), bool(u.prune_dead_chunks),
-                bool(self.prune_source_tail), bool(st.get("share_cfg_prefix")), smap, st["nvar"])
+                bool(self.prune_source_tail), bool(st.get("share_cfg_prefix")), smap, st["nvar"]) + \
+            (() if st["placement"] is None else (st["placement"],))
         g = st["variants"].get(vkey)
         if g is None:
             g = st["variants"][vkey] = GraphedStep(b["body"], preserve=(st["latents"],))
@@ -687,7 +757,7 @@ class I2VGenXLPipeline:
             negative_prompt_embeds=None, output_type="pil", return_dict=True, cross_attention_kwargs=None, clip_skip=1,
             fusion_steps=(0, 3), ddim_init_latents_t_idx=1, ddim_inv_prompt=None, obj_mask=None, obj_width_height=None,
             obj_ddim_latents_idx_offset=None, obj_random_noise_fusion=False, random_noise_ratio=0.0,
-            bg_inv_latents_path=None, obj_ddim_latents_path=None, obj_masks_tensors=None):
+            bg_inv_latents_path=None, obj_ddim_latents_path=None, obj_masks_tensors=None, obj_offsets=None):
         """PnP composition sampling.  ``obj_mask``: list of mask paths (preprocessed by ``mvoc_amd.utils.mask_preprocess``)
         or pass ``obj_masks_tensors`` = list of (float [1,4,F,h,w], bool [1,4,F,h,w]) directly.
 
@@ -695,7 +765,11 @@ class I2VGenXLPipeline:
         (one per video; a single generator is drawn K times), ``latents`` [K, 4, F, h, w], ``guidance_scale`` a float or a
         list, ``main_first_image`` a list of images and ``main_image_list`` a list of frame lists; ``num_videos_per_prompt`` =
         m repeats each prompt m times (K = len(prompt) * m).  The sources, masks, schedules and fusion settings are shared; the
-        call returns K videos (``frames[k]``).  Scalars mean what they mean in a single composition."""
+        call returns K videos (``frames[k]``).  Scalars mean what they mean in a single composition.
+
+        ``obj_offsets``: one entry per object, ``(dx, dy)`` or ``num_frames`` such pairs (a path), image pixels
+        in multiples of 8 -- the object is composed that far from where it sits in its source clip (``normalize_obj_offsets``;
+        translation only, shared by the variants, not with a frame shard).  None or all zeros: exactly a call without it."""
         from .utils import mask_preprocess
         # ---- the variants of this call (one with scalar arguments: the batch, kernels and launches of a single composition)
         m_rep = int(num_videos_per_prompt)
@@ -737,6 +811,10 @@ class I2VGenXLPipeline:
         c = self.conditioner
         n_obj = len(obj_ddim_latents_path)
         assert obj_mask is None or len(obj_mask) == n_obj
+        placement = normalize_obj_offsets(obj_offsets, n_obj, num_frames, self.vae_scale_factor)
+        if placement is not None and self.unet.shard is not None:
+            raise RuntimeError("obj_offsets do not combine with the frame shard: the section masks are cut to pixel slabs and a "
+                               "shift crosses slabs")
         # source de-duplication: roles showing the same image share ONE draw of the VAE posterior (prepare_image_latents samples
         # per role, :860-890) and one vision-tower pass -- else identical frames would give every role its own image latents and
         # no two roles could share a chunk (make_composition_state)
@@ -818,7 +896,8 @@ class I2VGenXLPipeline:
         if obj_masks_tensors is None:
             obj_masks_tensors = [mask_preprocess(m, self.device, H16, 1, 4, num_frames, downscale=8) for m in obj_mask]
         self.unet.check_variant_schedules(nvar)  # per-variant injection schedules are hook state (pnp_utils): one entry per variant
-        st = self.make_composition_state(latents, cond, obj_masks_tensors, scales if nvar > 1 else guidance_scale, variants=nvar)
+        st = self.make_composition_state(latents, cond, obj_masks_tensors, scales if nvar > 1 else guidance_scale, variants=nvar,
+                                         **({} if placement is None else {"placement": placement}))
         table, index = sched.coef_table(self.device, guidance_scale)
         if nvar > 1:  # [steps, K, 5]: a step's coefficient rows are one view, whatever K is
             table = torch.stack([sched.coef_table(self.device, g)[0] for g in scales], 1).contiguous()

@@ -363,7 +363,7 @@ class Transformer2DModel(_TransformerBase):
             ld = qkv.stride(0)
             ops.pnp_blend_tokens(q, masks, x2=k, frames=F, height=H, width=W, channels=c, chunk_stride=F * hw * ld,
                                  f_stride=hw * ld, p_stride=ld, base_chunk0=proc.inject_background, ndst=ndst, src_map=smap,
-                                 nvar=eng.variants, active=active)
+                                 nvar=eng.variants, active=active, **eng.place_kw(proc.mask, H, W))
         if ndst == 2 and eng.pair_destinations and active is not None:
             # per-variant schedules: only the variants whose q / k were just overwritten attend with u_k's q, k
             # equal to c_k's.  Per maximal run of equal activity: an injecting run [k0, k1) is one paired launch (its u and c
@@ -456,7 +456,8 @@ class TransformerTemporalModel(_TransformerBase):
                 ld = qkv.stride(0)
                 ops.pnp_blend_tokens(q, masks, x2=k, frames=F, height=H, width=W, channels=c, chunk_stride=F * hw * ld,
                                      f_stride=hw * ld, p_stride=ld, base_chunk0=proc.inject_background, ndst=ndst,
-                                     src_map=smap, nvar=eng.variants, active=eng.site_active(proc))
+                                     src_map=smap, nvar=eng.variants, active=eng.site_active(proc),
+                                     **eng.place_kw(proc.mask, H, W))
                 if eng._tail_site is self:  # (prune_source_tail) the last reader of the source chunks was this blend
                     r0 = (B - ndst * eng.variants) * F * hw
                     q, k, v, h, x = q[r0:], k[r0:], v[r0:], h[r0:], x[r0:]
@@ -671,6 +672,13 @@ class I2VGenXLUNet:
         # paired attention serves the K pairs in one launch.  1 = today's batch, kernels and launches.  Set and restored around
         # its forward by the composition loop, like source_chunks.  Not with a frame shard, not with shared_prefix_chunks.
         self.variants = 1
+        # Placement (pipeline.py obj_offsets): None, or a hashable tuple -- per object, per frame (dy, dx) on the
+        # latent grid (the masks' h x w).  Every injection site then reads object j of frame f at its shifted pixel through the
+        # _placed blend entries (the hook masks are in destination coordinates already: the pipeline shifts them once per call);
+        # the offsets of a site's H x W come from ops.level_offset.  None = today's calls.  Set and restored around its forward
+        # by the composition loop, like source_chunks; shared by the variants.  Not with a frame shard.
+        self.placement = None
+        self._place_cache = (None, {})
 
     def set_frame_shard(self, shard):
         """Frame-shard every forward over the ranks of ``shard`` (``mvoc_amd.frame_shard``): each rank receives the FULL
@@ -850,8 +858,36 @@ class I2VGenXLUNet:
             return None
         return nsrc, chunks
 
+    def place_table(self, mask_list, H, W):
+        """the ``place=`` argument of a site's blend at H x W: None without a placement, else the device table of per-(object,
+        frame) feature offsets, cached per (placement, H, W) and dropped when the placement changes"""
+        pl = self.placement
+        if pl is None:
+            return None
+        if self.shard is not None:
+            raise RuntimeError("a placement does not combine with the frame shard: the section masks are cut to pixel slabs "
+                               "and a shift crosses slabs")
+        if len(pl) != len(mask_list):
+            raise RuntimeError(f"placement holds offsets for {len(pl)} objects, the hooks carry {len(mask_list)} masks")
+        if self._place_cache[0] != pl:
+            self._place_cache = (pl, {})
+        mh, mw = self._all_frame_masks(mask_list)[0].shape[2:]
+        key = (H, W, mh, mw)
+        tab = self._place_cache[1].get(key)
+        if tab is None:
+            tab = self._place_cache[1][key] = ops.place_table(pl, H, W, mh, mw, self.device)
+        return tab
+
+    def place_kw(self, mask_list, H, W):
+        """keyword arguments of a site's blend call: none without a placement (exactly today's call), else ``place=``"""
+        tab = self.place_table(mask_list, H, W)
+        return {} if tab is None else {"place": tab}
+
     def pnp_batch(self, B, mask_list):
         """(ndst, source map) of an injection site's batch of B chunks (``check_pnp_batch`` under ``source_chunks``)"""
+        if self.placement is not None and self.shard is not None:
+            raise RuntimeError("a placement does not combine with the frame shard: the section masks are cut to pixel slabs "
+                               "and a shift crosses slabs")
         smap = self.pnp_src_map()
         if smap is not None and len(smap[1]) != len(mask_list):
             raise RuntimeError(f"source_chunks maps {len(smap[1])} objects, the hooks carry {len(mask_list)} masks")
@@ -953,7 +989,7 @@ class I2VGenXLUNet:
         ld = h.stride(0)
         ops.pnp_blend_tokens(h, hard, frames=F, height=H, width=W, channels=channels, chunk_stride=F * H * W * ld,
                              f_stride=H * W * ld, p_stride=ld, base_chunk0=True, ndst=ndst, src_map=smap, nvar=self.variants,
-                             active=None if site is None else self.site_active(site))
+                             active=None if site is None else self.site_active(site), **self.place_kw(mask_list, H, W))
         if getattr(h, "chan_sums", None) is not None:
             h.chan_sums = None  # rewritten in place: the producer's GroupNorm statistics no longer describe these rows
 
@@ -1122,7 +1158,7 @@ class I2VGenXLUNet:
         nchw = torch.empty((B * F, C, H, W), dtype=H16, device=self.device)
         nchw[:ns * F] = src.permute(0, 2, 1, 3, 4).reshape(ns * F, C, H, W)
         ops.pnp_blend_nchw(nchw, self.device_masks(co.mask)[1], frames=F, base_chunk0=True, ndst=ndst, src_map=smap,
-                           nvar=self.variants)  # (taken only when EVERY variant injects at conv_out)
+                           nvar=self.variants, **self.place_kw(co.mask, H, W))  # (taken only when EVERY variant injects at conv_out)
         return nchw.reshape(B, F, C, H, W).permute(0, 2, 1, 3, 4).contiguous()
 
     def spatial_transformers(self):
@@ -1245,7 +1281,7 @@ class I2VGenXLUNet:
             out = ops.tokens_to_ncfhw(y, B, co.cout, F, H, W)  # [B,C,F,h,w]
             nchw = out.permute(0, 2, 1, 3, 4).reshape(B * F, co.cout, H, W).contiguous()
             ops.pnp_blend_nchw(nchw, self.device_masks(co.mask)[1], frames=F, base_chunk0=True, ndst=ndst, src_map=smap,
-                               nvar=self.variants, active=self.site_active(co))
+                               nvar=self.variants, active=self.site_active(co), **self.place_kw(co.mask, H, W))
             out = nchw.reshape(B, F, co.cout, H, W).permute(0, 2, 1, 3, 4).contiguous()
         else:
             out = ops.tokens_to_ncfhw(y, B, co.cout, F, H, W)

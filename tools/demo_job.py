@@ -17,6 +17,10 @@ DESIGN.md 6i); the JSON line holds the composition-stage time and the mean devic
 --variant-thresholds a,b,.. gives variant k its own pnp_spatial_attn_t (the variants' `pnp` key); --sequential
 also runs the K compositions one by one in the same process and reports the ratio.
 
+--place "dx,dy;dx,dy" (opt-in): the entry's `obj_offset` (DESIGN.md 6k) -- one pair per object, image pixels in multiples of 8;
+the composition then places the objects that far from where they sit in their clips.  Reported like --variants (K = 1 unless
+--variants is given too).
+
 --shared-source (opt-in): the shape of MVOC's own demo entries, where the background and both objects point at ONE inversion
 directory and the same control frames.  One clip is inverted, then the composition runs with source de-duplication off and then
 on (composite.py --dedup_sources), in this process; the JSON line holds both composition-stage times (the sampling call without
@@ -352,7 +356,18 @@ class StageTimer:
                 "steps_timed": {k: len(v) for k, v in sorted(by.items())}}
 
 
-def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, thresholds=None, sequential=False):
+def parse_place(text):
+    """"dx,dy;dx,dy" -> [[dx, dy], [dx, dy]] (one pair per object)"""
+    try:
+        out = [[int(v) for v in item.split(",")] for item in text.split(";")]
+    except ValueError:
+        raise SystemExit(f"--place {text!r}: expected integers as dx,dy;dx,dy")
+    if any(len(p) != 2 for p in out):
+        raise SystemExit(f"--place {text!r}: every object needs dx,dy")
+    return out
+
+
+def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, thresholds=None, sequential=False, place=None):
     """K prompts and seeds over the boat_surf-shaped job (three distinct sources), one composition loop (composite.py `variants`).
     ``thresholds``: K values of pnp_spatial_attn_t, one per variant (the variants' `pnp` key); ``sequential``: after
     the one loop, the same K compositions one by one (single entries with the flat threshold) for the comparison."""
@@ -385,6 +400,8 @@ def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, threshol
         for v, th in zip(var, thresholds):
             v["pnp"] = {"pnp_spatial_attn_t": float(th)}
     centry = dict(boat_surf_entry(size), variants=var)
+    if place is not None:  # shared by the variants: an entry key
+        centry["obj_offset"] = [list(p) for p in place]
     with StageTimer(pl) as timer:
         composite.main(ct, [centry], dev, synthetic=True)
     res = timer.result()
@@ -395,6 +412,8 @@ def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, threshol
         for d in sorted(os.listdir(os.path.join(out_root, sfx))):
             files[d], where[d] = sorted(os.listdir(os.path.join(out_root, sfx, d))), sfx
     dirs = sorted(files)
+    if place is not None:
+        res["obj_offset"] = [list(p) for p in place]
     if thresholds is not None:
         res["variant_thresholds"] = [float(t) for t in thresholds]
         res["output_suffix_of"] = {d: where[d] for d in dirs}
@@ -402,6 +421,8 @@ def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, threshol
         seq = []
         for k in range(variants):
             e = dict(boat_surf_entry(size), edited_video_name=f"seq{k}", **{kk: vv for kk, vv in var[k].items() if kk != "pnp"})
+            if place is not None:
+                e["obj_offset"] = [list(p) for p in place]
             if thresholds is not None:
                 e["pnp_spatial_attn_t"] = float(thresholds[k])
             with StageTimer(pl) as t1:
@@ -437,11 +458,14 @@ if __name__ == "__main__":
                     help="with --variants K: K values of pnp_spatial_attn_t, one per variant (the variants' `pnp` key)")
     ap.add_argument("--sequential", action="store_true",
                     help="with --variants K: also run the K compositions one by one and report the ratio")
+    ap.add_argument("--place", type=str, default=None, metavar="dx,dy;dx,dy",
+                    help="place the objects at composition time: one dx,dy per object, image pixels in multiples of 8 (`obj_offset`)")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
-    if a.variants:
+    if a.variants or a.place:
         th = None if a.variant_thresholds is None else [float(x) for x in a.variant_thresholds.split(",")]
-        print(json.dumps(run_variants(a.frames, a.size, a.steps, a.keep, a.variants, th, a.sequential)), flush=True)
+        place = None if a.place is None else parse_place(a.place)
+        print(json.dumps(run_variants(a.frames, a.size, a.steps, a.keep, a.variants or 1, th, a.sequential, place)), flush=True)
     else:
         fn = run_shared_source if a.shared_source else run
         print(json.dumps(fn(a.frames, a.size, a.steps, a.keep)), flush=True)
