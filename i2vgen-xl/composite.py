@@ -11,6 +11,8 @@ An entry with ``variants: [{...}, ...]`` composes K prompts / seeds / guidance s
 (``merge_variants``; files under ``.../variant_00/``, ``variant_01/`` ...); a variant's ``pnp: {...}`` gives it injection
 thresholds of its own.  An entry's ``obj_offset: [[dx, dy], ...]`` (one item per object: a pair, or one pair per frame; image
 pixels in multiples of 8) places the objects at composition time (``placement_kwargs``; shared by the entry's variants).
+A variant's ``placement: [[dx, dy], ...]`` (the format of ``obj_offset``) places the objects for that variant alone
+(``variant_placement_kwargs``); a variant without the key takes the entry's ``obj_offset``, or none.
 """
 import argparse
 import json
@@ -80,9 +82,10 @@ def output_suffix(config):
 
 # what one variant of an entry may override; every other key is shared by the variants of a call (sources, masks, the entry's
 # schedules, fusion settings: the source chunks are computed once for all of them).  "pnp" is a dict of injection thresholds
-# of the variant's own (any of PNP_KEYS) -- the flat threshold keys stay the entry's
+# of the variant's own (any of PNP_KEYS) -- the flat threshold keys stay the entry's.  "placement" is the variant's
+# own object placement in the format of the entry's ``obj_offset`` -- ``obj_offset`` itself stays the entry's
 VARIANT_KEYS = ("editing_prompt", "editing_negative_prompt", "seed", "cfg", "edited_first_frame_path",
-                "edited_contorl_frame_path_main", "pnp")
+                "edited_contorl_frame_path_main", "pnp", "placement")
 PNP_KEYS = ("pnp_f_t", "pnp_spatial_attn_t", "pnp_temp_attn_t")
 MAX_VARIANTS = 8
 
@@ -140,6 +143,18 @@ def placement_kwargs(config):
     return {"obj_offsets": plain(config.obj_offset)}
 
 
+def variant_placement_kwargs(config, variants):
+    """keyword arguments of the sampling call for the placements of an entry and its variants (``merge_variants``): when no
+    variant sets ``placement`` exactly ``placement_kwargs(config)``; else ``variant_obj_offsets`` = one item per variant -- the
+    variant's ``placement``, or the entry's ``obj_offset`` (None without one) for a variant that does not set the key."""
+    if variants is None or not any("placement" in c and c.placement is not None for c in variants):
+        return placement_kwargs(config)
+    plain = lambda v: [plain(x) for x in v] if hasattr(v, "__iter__") and not isinstance(v, (str, bytes)) else v
+    shared = placement_kwargs(config).get("obj_offsets")
+    return {"variant_obj_offsets": [plain(c.placement) if "placement" in c and c.placement is not None else shared
+                                    for c in variants]}
+
+
 def variant_output_dir(config, k):
     """``<output_dir>/<output_suffix of the variant's merged config>/variant_{k:02d}``"""
     return os.path.join(config.output_dir, output_suffix(config), f"variant_{k:02d}")
@@ -186,7 +201,7 @@ def main(template_config, configs_list, device, synthetic=False, dedup_sources=F
                   obj_ddim_latents_path=config.obj_ddim_latents_path,
                   obj_ddim_latents_idx_offset=config.obj_ddim_latents_idx_offset,
                   obj_random_noise_fusion=config.obj_random_noise_fusion, fusion_steps=config.fusion_step,
-                  **placement_kwargs(config))
+                  **variant_placement_kwargs(config, variants))
         if variants is None:
             output_dirs, configs = [os.path.join(config.output_dir, output_suffix(config))], [config]
         else:  # K variants in one loop: per-variant prompt / negative prompt / seed / cfg / main image, everything else shared

@@ -345,6 +345,26 @@ int mvoc_pnp_blend_scatter_tokens_placed(const mvoc_pnp_desc* d, int32_t nsrc, c
                                          uint32_t active, const int32_t* place, void* stream);
 int mvoc_pnp_blend_scatter_nchw_placed(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
                                        uint32_t active, const int32_t* place, void* stream);
+/* Per-variant placement: the _placed entries with an offset table and masks PER VARIANT.  `place` is a DEVICE
+ * table of int32 pairs [nvar][nobj][frames][2] = (dfy, dfx) for this call's height x width; variant k reads object j of frame f
+ * at (py - dfy, px - dfx) taken from row (k * nobj + j) * frames + f.  d->masks points at [nvar][nobj][frames][mask_h][mask_w]:
+ * variant k's masks in ITS destination coordinates, sampled at the destination pixel by the nearest rule above.  Absent objects,
+ * the 64-bit source pixel, the three fp16-rounded ops per object, object order, ndst, base_chunk0, the source map and `active`
+ * are those of _placed; the chunks of a variant whose bit is clear are neither read nor written.  With base_chunk0 != 0 the base
+ * vector is loaded once per work item and every injecting variant blends it with its own objects.  Variant k's destination
+ * rows are bit-identical to the _placed entry with nvar = 1 on that variant's own [sources.., (u_k,) c_k] batch with table k
+ * and masks k; nvar = 1 is the _placed entry, nvar equal tables with equal masks are the _placed entry with that table.
+ * Bytes counted per launch (MvocProfScope), with on = popcount(active), E = frames*height*width*channels, T = tensors (1 or 2):
+ *     T * (2*E * (on * distinct object chunks + (base_chunk0 ? 1 : on) + ndst * on) + 2 * on * nobj*frames*height*width)
+ *       + 8 * nvar*nobj*frames
+ * i.e. each injecting variant reads its objects at its own pixels and one mask value per object and pixel, the base is read
+ * once when it is chunk 0 and once per injecting variant otherwise, ndst * on chunks are written, and the table is read.
+ * Requires a non-NULL table, 1 <= nvar <= 8, 1 <= active < (1u << nvar) and a valid map (else -1 and an error text, nothing
+ * written). */
+int mvoc_pnp_blend_scatter_tokens_placed_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
+                                                  uint32_t active, const int32_t* place, void* stream);
+int mvoc_pnp_blend_scatter_nchw_placed_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
+                                                uint32_t active, const int32_t* place, void* stream);
 /* Zero-filled per-frame integer translation of contiguous fp16 planes [nplane][frames][h][w] (src != dst):
  *     dst[pl][f][y][x] = src[pl][f][y - dy_f][x - dx_f], or 0 where that pixel lies outside the plane
  * `offsets`: DEVICE int32 pairs [frames][2] = (dy_f, dx_f), shared by the nplane planes -- the planes of one call belong to one

@@ -505,6 +505,128 @@ __global__ __launch_bounds__(256) void pnp_nchw_placed_kernel(const PnpArgs p, c
   }
 }
 
+// ---- per-variant placement ------------------------------------------------------------------------
+// The _placed kernels with an offset table and masks PER VARIANT: place is [nvar][nobj][frames][2], masks are
+// [nvar][nobj][frames][mask_h][mask_w] (variant k's masks in ITS destination coordinates).  Variant k reads object j of frame f
+// at (py - dfy, px - dfx) from row (k * nobj + j) * frames + f.  The variant loop is the OUTER loop and only one variant's NOBJ
+// object vectors are live at a time; next to them the kernels keep the base vector and the loop state, so they need more
+// registers than the _placed kernels (tokens 26 / 39 / 52 / 62 VGPRs against 18 / 26 / 32 / 37, nchw<8> 40 / 112 / 132 / 154 against
+// 30 / 78 / 94 / 110; no scratch; DESIGN.md 6l has the table and what it costs).  With base_chunk0 the base vector
+// is loaded once per work item and every injecting variant blends it with its own objects (the blend differs per variant, so
+// it cannot be shared as in the kernels above); otherwise variant k's base is its own cond chunk.  The arithmetic per variant
+// is blend16_h in object order, absent = (0, 0) entering the arithmetic.  Kernels of their own.
+template <int NOBJ>
+__global__ __launch_bounds__(256) void pnp_tokens_placed_variants_kernel(const PnpArgs p, const int nvar, const unsigned active,
+                                                                         const int* __restrict__ place) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= p.total) return;
+  half_t* x = p.x[blockIdx.y];
+  const int c8n = p.channels >> 3;
+  const int c8 = (int)(idx % c8n);
+  const long fp = idx / c8n;
+  const int hw = p.height * p.width;
+  const int f = (int)(fp / hw), px = (int)(fp % hw);
+  const int py = px / p.width, pxx = px - py * p.width;
+  const int my = nearest_src(py, p.sy, p.mask_h), mx = nearest_src(pxx, p.sx, p.mask_w);
+  const long foff = (long)f * p.f_stride + c8 * 8;
+  const long off = foff + (long)px * p.p_stride;
+  const long mvar = (long)NOBJ * p.frames * p.mask_h * p.mask_w;  // masks of one variant
+  half8_t bv;
+  if (p.base_chunk0) bv = *reinterpret_cast<const half8_t*>(x + off);
+  for (int k = 0; k < nvar; ++k) {
+    if (!((active >> k) & 1u)) continue;
+    const int* pl = place + (long)k * NOBJ * p.frames * 2;
+    const half_t* mk = p.masks + k * mvar;
+    half8_t ov[NOBJ];
+    half_t m[NOBJ];
+#pragma unroll
+    for (int j = 0; j < NOBJ; ++j) {
+      long spix;
+      const bool in = placed_src(pl, j, p.frames, f, py, pxx, p.height, p.width, spix);
+      m[j] = (half_t)0.0f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) ov[j][e] = (half_t)0.0f;
+      if (in) {
+        m[j] = mk[(((long)j * p.frames + f) * p.mask_h + my) * p.mask_w + mx];
+        ov[j] = *reinterpret_cast<const half8_t*>(x + obj_chunk<true>(p, j) * p.chunk_stride + foff + spix * p.p_stride);
+      }
+    }
+    half_t* cond = x + var_dst(p, nvar, p.ndst - 1, k) * p.chunk_stride + off;
+    if (!p.base_chunk0) bv = *reinterpret_cast<const half8_t*>(cond);
+    half8_t o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      half_t inj = bv[e];
+#pragma unroll
+      for (int j = 0; j < NOBJ; ++j) inj = blend16_h(inj, ov[j][e], m[j]);
+      o[e] = inj;
+    }
+    if (p.ndst == 2) *reinterpret_cast<half8_t*>(x + var_dst(p, nvar, 0, k) * p.chunk_stride + off) = o;
+    *reinterpret_cast<half8_t*>(cond) = o;
+  }
+}
+
+// NCHW: object values one pixel at a time (as pnp_nchw_placed_kernel); base and destinations vectorised when VEC == 8
+template <int VEC, int NOBJ>
+__global__ __launch_bounds__(256) void pnp_nchw_placed_variants_kernel(const PnpArgs p, const int nvar, const unsigned active,
+                                                                       const int* __restrict__ place) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= p.total) return;
+  half_t* x = p.x[blockIdx.y];
+  const int hw = p.height * p.width;
+  const int pvn = hw / VEC;
+  const int pv = (int)(idx % pvn);
+  const long fc = idx / pvn;
+  const int f = (int)(fc / p.channels);
+  const long off = fc * hw + (long)pv * VEC;  // (f*C + c)*HW + p
+  const long chunk = (long)p.frames * p.channels * hw;
+  const long mvar = (long)NOBJ * p.frames * p.mask_h * p.mask_w;  // masks of one variant
+  half_t base[VEC];
+  if (p.base_chunk0) ld_vec<VEC>(base, x + off);
+  for (int k = 0; k < nvar; ++k) {
+    if (!((active >> k) & 1u)) continue;
+    const int* pl = place + (long)k * NOBJ * p.frames * 2;
+    const half_t* mk = p.masks + k * mvar;
+    // The per-pixel terms (row / column, mask index, 64-bit bases) do not depend on k; hoisted out of the variant loop they
+    // stay live across it (202 VGPRs at NOBJ = 4, VEC = 8).  The empty asm makes pv opaque per iteration, so they are formed
+    // inside the loop like the object values (154).
+    int pvk = pv;
+    asm volatile("" : "+v"(pvk));
+    half_t ov[NOBJ][VEC];
+    half_t m[NOBJ][VEC];
+#pragma unroll
+    for (int j = 0; j < NOBJ; ++j) {
+      const half_t* src = x + obj_chunk<true>(p, j) * chunk + fc * hw;
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        const int px = pvk * VEC + e;
+        const int py = px / p.width, pxx = px - py * p.width;
+        long spix;
+        const bool in = placed_src(pl, j, p.frames, f, py, pxx, p.height, p.width, spix);
+        m[j][e] = (half_t)0.0f;
+        ov[j][e] = (half_t)0.0f;
+        if (in) {
+          const int my = nearest_src(py, p.sy, p.mask_h), mx = nearest_src(pxx, p.sx, p.mask_w);
+          m[j][e] = mk[(((long)j * p.frames + f) * p.mask_h + my) * p.mask_w + mx];
+          ov[j][e] = src[spix];
+        }
+      }
+    }
+    half_t* cond = x + var_dst(p, nvar, p.ndst - 1, k) * chunk + off;
+    if (!p.base_chunk0) ld_vec<VEC>(base, cond);
+    half_t tmp[VEC];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      half_t inj = base[e];
+#pragma unroll
+      for (int j = 0; j < NOBJ; ++j) inj = blend16_h(inj, ov[j][e], m[j][e]);
+      tmp[e] = inj;
+    }
+    if (p.ndst == 2) st_vec<VEC>(x + var_dst(p, nvar, 0, k) * chunk + off, tmp);
+    st_vec<VEC>(cond, tmp);
+  }
+}
+
 // zero-filled per-frame integer translation of [nplane][F][h][w]: dst[pl, f, y, x] = src[pl, f, y - dy_f, x - dx_f] or 0;
 // offsets = F int32 pairs (dy_f, dx_f) on the device, shared by the planes
 __global__ __launch_bounds__(256) void shift_planes_kernel(const half_t* __restrict__ src, half_t* __restrict__ dst, int frames,
@@ -897,6 +1019,89 @@ extern "C" int mvoc_pnp_blend_scatter_nchw_placed(const mvoc_pnp_desc* d, int32_
     default: launch_nchw_placed_n<4>(vec, grid, s, a, nvar, active, pl); break;
   }
   return mvoc_check_launch("pnp_nchw_placed_kernel");
+}
+
+namespace {
+
+// _placed_variants: the _placed contract with a table and masks per variant.  Traffic in chunks: every injecting variant reads
+// the distinct object chunks at its own pixels (nobjc each) and writes ndst chunks; the base is read once when it is chunk 0,
+// else once per injecting variant
+int fill_placed_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar, uint32_t active,
+                         const void* place, PnpArgs& a, double& chunks, int& on) {
+  double unused = 0;
+  if (int rc = fill_placed(d, nsrc, obj_chunk, nvar, active, place, a, unused)) return rc;
+  unsigned seen = 0;
+  for (int j = 0; j < d->nobj; ++j) seen |= 1u << obj_chunk[j];
+  on = __builtin_popcount(active);
+  chunks = (double)on * __builtin_popcount(seen) + (d->base_chunk0 ? 1 : on) + (double)a.ndst * on;
+  return 0;
+}
+
+template <int NOBJ>
+void launch_nchw_placed_variants_n(bool vec, dim3 grid, hipStream_t s, const PnpArgs& a, int nvar, unsigned active,
+                                   const int* place) {
+  if (vec)
+    hipLaunchKernelGGL((pnp_nchw_placed_variants_kernel<8, NOBJ>), grid, dim3(256), 0, s, a, nvar, active, place);
+  else
+    hipLaunchKernelGGL((pnp_nchw_placed_variants_kernel<1, NOBJ>), grid, dim3(256), 0, s, a, nvar, active, place);
+}
+
+}  // namespace
+
+extern "C" int mvoc_pnp_blend_scatter_tokens_placed_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
+                                                             int32_t nvar, uint32_t active, const int32_t* place, void* stream) {
+  PnpArgs a;
+  double chunks = 0;
+  int on = 0;
+  if (int rc = fill_placed_variants(d, nsrc, obj_chunk, nvar, active, place, a, chunks, on)) return rc;
+  MVOC_REQUIRE(d->channels % 8 == 0 && d->chunk_stride % 8 == 0 && d->f_stride % 8 == 0 && d->p_stride % 8 == 0, -2,
+               "pnp tokens: channels/strides must be multiples of 8");
+  a.total = (long)d->frames * d->height * d->width * (d->channels / 8);
+  const long nblk = (a.total + 255) / 256;
+  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "pnp tokens: grid too large");
+  const int ntens = d->x2 ? 2 : 1;
+  hipStream_t s = (hipStream_t)stream;
+  const double elems = (double)d->frames * d->height * d->width * d->channels;
+  MvocProfScope prof(MVOC_FAM_PNP, s,
+                     ntens * (elems * 2.0 * chunks + 2.0 * on * d->nobj * d->frames * d->height * d->width) +
+                         8.0 * nvar * d->nobj * d->frames);
+  const dim3 grid((unsigned)nblk, ntens);
+  const unsigned act = active;
+  const int* pl = (const int*)place;
+  switch (d->nobj) {
+    case 1: hipLaunchKernelGGL(pnp_tokens_placed_variants_kernel<1>, grid, dim3(256), 0, s, a, (int)nvar, act, pl); break;
+    case 2: hipLaunchKernelGGL(pnp_tokens_placed_variants_kernel<2>, grid, dim3(256), 0, s, a, (int)nvar, act, pl); break;
+    case 3: hipLaunchKernelGGL(pnp_tokens_placed_variants_kernel<3>, grid, dim3(256), 0, s, a, (int)nvar, act, pl); break;
+    default: hipLaunchKernelGGL(pnp_tokens_placed_variants_kernel<4>, grid, dim3(256), 0, s, a, (int)nvar, act, pl); break;
+  }
+  return mvoc_check_launch("pnp_tokens_placed_variants_kernel");
+}
+
+extern "C" int mvoc_pnp_blend_scatter_nchw_placed_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
+                                                           int32_t nvar, uint32_t active, const int32_t* place, void* stream) {
+  PnpArgs a;
+  double chunks = 0;
+  int on = 0;
+  if (int rc = fill_placed_variants(d, nsrc, obj_chunk, nvar, active, place, a, chunks, on)) return rc;
+  const long hw = (long)d->height * d->width;
+  const bool vec = hw % 8 == 0;
+  a.total = (long)d->frames * d->channels * (vec ? hw / 8 : hw);
+  const long nblk = (a.total + 255) / 256;
+  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "pnp nchw: grid too large");
+  const int ntens = d->x2 ? 2 : 1;
+  hipStream_t s = (hipStream_t)stream;
+  const double elems = (double)d->frames * hw * d->channels;
+  MvocProfScope prof(MVOC_FAM_PNP, s,
+                     ntens * (elems * 2.0 * chunks + 2.0 * on * d->nobj * d->frames * hw) + 8.0 * nvar * d->nobj * d->frames);
+  const dim3 grid((unsigned)nblk, ntens);
+  const int* pl = (const int*)place;
+  switch (d->nobj) {
+    case 1: launch_nchw_placed_variants_n<1>(vec, grid, s, a, nvar, active, pl); break;
+    case 2: launch_nchw_placed_variants_n<2>(vec, grid, s, a, nvar, active, pl); break;
+    case 3: launch_nchw_placed_variants_n<3>(vec, grid, s, a, nvar, active, pl); break;
+    default: launch_nchw_placed_variants_n<4>(vec, grid, s, a, nvar, active, pl); break;
+  }
+  return mvoc_check_launch("pnp_nchw_placed_variants_kernel");
 }
 
 extern "C" int mvoc_shift_planes_f16(const void* src, void* dst, int32_t nplane, int32_t frames, int32_t h, int32_t w,

@@ -14,7 +14,7 @@ from ._ffi import (A_CONV3X3, A_PLAIN, A_TEMPORAL3, ACT_GEGLU, ACT_GELU, ACT_NON
                    PnpDesc, TAttnDesc, TFusedDesc, XsDesc, check, lib)
 
 __all__ = ["linear", "conv3x3", "tconv3", "flash_attn", "temporal_attn", "groupnorm", "groupnorm_moments", "groupnorm_apply_moments", "layernorm", "pnp_blend_tokens",
-           "pnp_blend_nchw", "level_offset", "level_offsets", "place_table", "shift_planes", "ddim_step", "latent_fusion", "timestep_embedding", "act", "add", "conv3x3_small",
+           "pnp_blend_nchw", "level_offset", "level_offsets", "place_table", "place_table_variants", "shift_planes", "ddim_step", "latent_fusion", "timestep_embedding", "act", "add", "conv3x3_small",
            "adaptive_avgpool", "ncfhw_to_tokens", "tokens_to_ncfhw", "temporal_encoder4", "conv1x1_small", "softmax_rows", "ACT_NONE", "ACT_GEGLU",
            "ACT_SILU", "ACT_GELU"]
 
@@ -496,6 +496,11 @@ def layernorm(x, gamma, beta, eps=1e-5, out=None):
 
 def _pnp_desc(x, x2, masks, chunk_stride, f_stride, p_stride, frames, height, width, channels, base_chunk0, ndst=2):
     _chk(x, "x"), _chk(x2, "x2"), _chk(masks, "masks")
+    if masks.dim() == 5 and masks.is_contiguous() and masks.shape[2] == frames:
+        # per-variant placement: a [K, nobj, F, mh, mw] stack.  The descriptor has no field for K: it takes the
+        # stack's pointer (variant 0 first) and one variant's dims; K and the stack's shape are checked against the 4-D table by
+        # _check_place_variants, and both blend functions refuse a stack that comes without such a table before any launch
+        masks = masks[0]
     if masks.dim() != 4 or not masks.is_contiguous() or masks.shape[1] != frames:
         raise RuntimeError(f"pnp: masks must be contiguous [nobj, F, mh, mw] fp16, got {tuple(masks.shape)}")
     d = PnpDesc()
@@ -553,11 +558,18 @@ def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride,
     ``masks`` are in destination coordinates -- the ``_placed`` entry, whatever ``nvar`` / ``src_map`` / ``active`` are."""
     d = _pnp_desc(x, x2, masks, chunk_stride, f_stride, p_stride, frames, height, width, channels, base_chunk0, ndst)
     active = _active_mask(active, nvar, "pnp_blend_tokens")
+    if masks.dim() == 5 and (place is None or place.dim() != 4):
+        raise RuntimeError("pnp_blend_tokens: a [K, nobj, F, mh, mw] mask stack needs place= as an int32 [K, nobj, F, 2] table")
     if nvar != 1 or place is not None:
         nsrc, chunks = _variant_map(src_map, d.nobj)
         last = (nsrc + (int(ndst) or 2) * int(nvar) - 1) * chunk_stride
         _check_variants(x, x2, nvar, last + (frames - 1) * f_stride + (height * width - 1) * p_stride + channels,
                         "pnp_blend_tokens")
+        if _check_place_variants(place, masks, nvar, d.nobj, frames, "pnp_blend_tokens"):
+            check(lib.mvoc_pnp_blend_scatter_tokens_placed_variants(C.byref(d), nsrc, chunks, int(nvar), _all_or(active, nvar),
+                                                                    place.data_ptr(), _stream()),
+                  "pnp_blend_scatter_tokens_placed_variants")
+            return x
         if place is not None:
             _check_place(place, d.nobj, frames, "pnp_blend_tokens")
             check(lib.mvoc_pnp_blend_scatter_tokens_placed(C.byref(d), nsrc, chunks, int(nvar), _all_or(active, nvar),
@@ -585,9 +597,16 @@ def pnp_blend_nchw(x, masks, *, frames, x2=None, base_chunk0=True, ndst=2, src_m
         raise RuntimeError("pnp_blend_nchw: x must be contiguous [N, C, H, W]")
     d = _pnp_desc(x, x2, masks, 0, 0, 0, frames, x.shape[2], x.shape[3], x.shape[1], base_chunk0, ndst)
     active = _active_mask(active, nvar, "pnp_blend_nchw")
+    if masks.dim() == 5 and (place is None or place.dim() != 4):
+        raise RuntimeError("pnp_blend_nchw: a [K, nobj, F, mh, mw] mask stack needs place= as an int32 [K, nobj, F, 2] table")
     if nvar != 1 or place is not None:
         nsrc, chunks = _variant_map(src_map, d.nobj)
         _check_variants(x, x2, nvar, (nsrc + (int(ndst) or 2) * int(nvar)) * frames * x[0].numel(), "pnp_blend_nchw")
+        if _check_place_variants(place, masks, nvar, d.nobj, frames, "pnp_blend_nchw"):
+            check(lib.mvoc_pnp_blend_scatter_nchw_placed_variants(C.byref(d), nsrc, chunks, int(nvar), _all_or(active, nvar),
+                                                                  place.data_ptr(), _stream()),
+                  "pnp_blend_scatter_nchw_placed_variants")
+            return x
         if place is not None:
             _check_place(place, d.nobj, frames, "pnp_blend_nchw")
             check(lib.mvoc_pnp_blend_scatter_nchw_placed(C.byref(d), nsrc, chunks, int(nvar), _all_or(active, nvar),
@@ -638,6 +657,38 @@ def _check_place(place, nobj, frames, what):
     _chk(place, "place", torch.int32)
     if tuple(place.shape) != (nobj, frames, 2) or not place.is_contiguous():
         raise RuntimeError(f"{what}: place must be a contiguous int32 [nobj = {nobj}, F = {frames}, 2] table, got {tuple(place.shape)}")
+
+
+def place_table_variants(placements, height, width, mask_h, mask_w, device):
+    """the device table the ``_placed_variants`` blend entries read: int32 [K, nobj, F, 2], row k = ``place_table`` of
+    ``placements[k]`` (the same rule, ``level_offset``, and the same int32 refusal)"""
+    if not placements:
+        raise RuntimeError("place_table_variants: needs at least one variant's placement")
+    tabs = []
+    for k, pl in enumerate(placements):
+        try:
+            tabs.append(place_table(pl, height, width, mask_h, mask_w, "cpu"))
+        except RuntimeError as e:
+            raise RuntimeError(f"place_table_variants: variant {k}: {e}") from None
+    if len({tuple(t.shape) for t in tabs}) != 1:
+        raise RuntimeError(f"place_table_variants: the variants' tables differ in shape: {[tuple(t.shape) for t in tabs]}")
+    return torch.stack(tabs).to(device).contiguous()
+
+
+def _check_place_variants(place, masks, nvar, nobj, frames, what):
+    """True when ``place`` / ``masks`` are the per-variant pair (4-D table + 5-D mask stack); a 3-D table with
+    4-D masks is the shared placement (False); a mixed pair is an error"""
+    if place is None or (place.dim() != 4 and masks.dim() != 5):
+        return False
+    _chk(place, "place", torch.int32)
+    nvar = int(nvar)
+    if tuple(place.shape) != (nvar, nobj, frames, 2) or not place.is_contiguous():
+        raise RuntimeError(f"{what}: place must be a contiguous int32 [K = {nvar}, nobj = {nobj}, F = {frames}, 2] table with a "
+                           f"[K, nobj, F, mh, mw] mask stack, got {tuple(place.shape)}")
+    if masks.dim() != 5 or tuple(masks.shape[:3]) != (nvar, nobj, frames) or not masks.is_contiguous():
+        raise RuntimeError(f"{what}: a [K, nobj, F, 2] table needs masks as a contiguous [K = {nvar}, nobj = {nobj}, F = {frames}, "
+                           f"mh, mw] stack, got {tuple(masks.shape)}")
+    return True
 
 
 def _all_or(active, nvar):

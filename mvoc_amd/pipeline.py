@@ -16,6 +16,7 @@ iteration is one captured hipGraph replay (~2000 kernel launches otherwise).
 import hashlib
 import logging
 import os
+import weakref
 from copy import deepcopy
 
 import torch
@@ -215,6 +216,34 @@ def normalize_obj_offsets(obj_offsets, n_obj, num_frames, factor=8):
     return tuple(out)
 
 
+def resolve_variant_obj_offsets(variant_obj_offsets, nvar, n_obj, num_frames, factor=8):
+    """``variant_obj_offsets`` of the sampling call: K = ``nvar`` items, each None or a value ``obj_offsets``
+    accepts, normalised per variant by ``normalize_obj_offsets`` -> (shared placement or None, per-variant placements or None):
+      (None, None)     nothing to move (no argument, or every item None / all zeros): exactly a call without the argument
+      (placement, None) every variant resolves to the same placement: exactly the shared ``obj_offsets`` call
+      (None, (p_0..p_{K-1})) placements differ: per-variant placement; a variant that is not placed carries all-zero offsets
+    Anything else is a ValueError that names the variant (and, from ``normalize_obj_offsets``, the object)."""
+    if variant_obj_offsets is None:
+        return None, None
+    if not isinstance(variant_obj_offsets, (list, tuple)):
+        raise ValueError(f"variant_obj_offsets: needs a list of {nvar} items (one per variant), got {variant_obj_offsets!r}")
+    items = list(variant_obj_offsets)
+    if len(items) != nvar:
+        raise ValueError(f"variant_obj_offsets: {len(items)} entries for {nvar} variants (one per variant)")
+    pls = []
+    for k, item in enumerate(items):
+        try:
+            pls.append(normalize_obj_offsets(item, n_obj, num_frames, factor))
+        except ValueError as e:
+            raise ValueError(f"variant_obj_offsets: variant {k}: {e}") from None
+    if all(p is None for p in pls):
+        return None, None
+    if all(p == pls[0] for p in pls):
+        return pls[0], None
+    zero = tuple(((0, 0),) * num_frames for _ in range(n_obj))
+    return None, tuple(zero if p is None else p for p in pls)
+
+
 def crosses_gemm_offset_line(nb, frames, h, w, width0):
     """the eight-phase GEMM tiles address their operands with 32-bit byte offsets (gemm.hip g8_ok): the widest level-0 tensor
     of a forward, the feed-forward's [nb * F * h * w, 4 * width0] fp16, must stay under 2 GB for them to be chosen"""
@@ -231,6 +260,15 @@ def _per_variant(value, n_prompts, m, what, is_scalar):
     if len(value) == n_prompts:
         return [v for v in value for _ in range(m)]
     raise ValueError(f"{what}: {len(value)} entries for {n_prompts} prompts x {m} videos per prompt")
+
+
+class CompositionState(dict):
+    """the composition loop's state: a dict that can be referred to weakly.  The closures the state itself holds (``build_map``,
+    the iteration bodies of its batches, which its captured graphs keep) reach it through a weak reference, so a dropped state is
+    freed at once, by reference count, with its captured graphs.  As a reference cycle it would wait for the cyclic collector,
+    and a collection that falls into a LATER state's graph capture destroys the graphs there: HIP refuses that ("operation not
+    permitted when stream is capturing") and the process ends."""
+    __slots__ = ("__weakref__",)
 
 
 class GraphedStep:
@@ -610,7 +648,19 @@ class I2VGenXLPipeline:
             moved.append((s16.to(soft.dtype), h16.to(hard.dtype)))
         return moved, table
 
-    def make_composition_state(self, latents, cond, masks, guidance_scale, dedup_sources=None, variants=1, placement=None):
+    def place_variant_masks(self, masks, variant_placements):
+        """the call's masks moved once per variant (``place_masks`` with each variant's placement) ->
+        dict(place_dev = per variant the device table int32 [nobj, F, 2] of its latent-grid offsets,
+             masks = (soft, hard) fp16 [K, nobj, F, h, w] stacks for the engine (``unet.variant_masks``),
+             fusion_masks = per variant the soft masks [nobj, 1, 4, F, h, w] fp16 of the fusion steps)"""
+        moved = [self.place_masks(masks, pl) for pl in variant_placements]
+        first = lambda t: t.reshape(-1, *t.shape[-3:])[0].to(self.device, H16)  # as the engine forms its device masks
+        return {"place_dev": [tab for _, tab in moved],
+                "masks": tuple(torch.stack([torch.stack([first(m[i]) for m in mk]) for mk, _ in moved]).contiguous() for i in (0, 1)),
+                "fusion_masks": [torch.stack([m[0].to(self.device, H16) for m in mk]).contiguous() for mk, _ in moved]}
+
+    def make_composition_state(self, latents, cond, masks, guidance_scale, dedup_sources=None, variants=1, placement=None,
+                               variant_placements=None):
         """static buffers + the captured iteration variants of the composition loop.
         cond: dict(encoder_hidden_states [n,77,D], image_embeddings [n,F,D], image_latents_first, image_latents, fps).
         The state keeps its OWN copy of ``cond``: the hoisted conditioning (``prepare_conditioning``) and the shared-CFG-prefix
@@ -621,8 +671,23 @@ class I2VGenXLPipeline:
         ``variants`` = K > 1: ``latents`` is [K, 4, F, h, w], ``cond`` rows follow ``variant_layout`` ([bg, obj.., u_1..u_K,
         c_1..c_K]), ``guidance_scale`` is a float or K floats (all > 1 or none), a step's coefficient rows are [K, 5].
         ``placement`` (``normalize_obj_offsets``; None: objects stay where they are): ``masks`` come in the objects' source
-        coordinates and are moved ONCE, here, to destination coordinates -- the state's masks everywhere (hooks, fusion)."""
+        coordinates and are moved ONCE, here, to destination coordinates -- the state's masks everywhere (hooks, fusion).
+        ``variant_placements`` (``resolve_variant_obj_offsets``; not with ``placement``): K placements, one per
+        variant.  Each variant's masks are moved once, here; the engine takes them as (soft, hard) [K, nobj, F, h, w] stacks,
+        the fusion steps each variant's own.  The hooks keep ``masks`` as they came (shape checks and the mask key)."""
         cond = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in cond.items()}
+        vstate = None
+        if variant_placements is not None:
+            if placement is not None:
+                raise ValueError("variant_placements and placement are both given: a call places its objects per variant or "
+                                 "once for all variants")
+            if self.unet.shard is not None:
+                raise RuntimeError("variant_placements do not combine with the frame shard: the section masks are cut to pixel "
+                                   "slabs and a shift crosses slabs")
+            if len(variant_placements) != int(variants):
+                raise ValueError(f"variant_placements: {len(variant_placements)} placements for {int(variants)} variants")
+            variant_placements = tuple(variant_placements)
+            vstate = self.place_variant_masks(masks, variant_placements)
         place_dev = None
         if placement is not None:
             if self.unet.shard is not None:
@@ -643,14 +708,17 @@ class I2VGenXLPipeline:
             raise RuntimeError("variants > 1 do not combine with the frame shard: run one composition per call")
         dev = self.device
         dedup = self.dedup_sources if dedup_sources is None else bool(dedup_sources)
-        st = {"latents": latents.clone(), "inp": torch.empty((nb,) + tuple(latents.shape[1:]), dtype=H16, device=dev),
+        st = CompositionState()
+        st.update({"latents": latents.clone(), "inp": torch.empty((nb,) + tuple(latents.shape[1:]), dtype=H16, device=dev),
               "t": torch.zeros(1, dtype=torch.float32, device=dev),
               "coef": torch.zeros(5 if nvar == 1 else (nvar, 5), dtype=torch.float32, device=dev),
               "masks": masks, "variants": {}, "cond": cond, "n_obj": n_obj, "nvar": nvar,
               "fusion_masks": torch.stack([m[0].to(dev, H16) for m in masks]).contiguous(),
               "fusion_objs": torch.empty((n_obj, 1) + tuple(latents.shape[1:]), dtype=H16, device=dev), "maps": {},
-              "placement": placement, "place_dev": place_dev, "place_tables": []}
-        st["build_map"] = lambda smap: self._composition_batch(st, smap, do_cfg)
+              "placement": placement, "place_dev": place_dev, "place_tables": [],
+              "variant_placements": variant_placements, "vplace": vstate})
+        weak = weakref.ref(st)  # (the caller holds the state for as long as it steps it)
+        st["build_map"] = lambda smap: self._composition_batch(weak(), smap, do_cfg)
         st["maps"][None] = st["build_map"](None)
 
         # classifier-free guidance: the unconditional and the conditional chunk receive the same latent (below); when their image
@@ -682,7 +750,11 @@ class I2VGenXLPipeline:
                                                   mcond["image_latents"], mcond["image_embeddings"],
                                                   mcond["encoder_hidden_states"], False)
 
+        weak = weakref.ref(st)  # the state holds this body (and its captured graph): no cycle back to it, see CompositionState
+        del st
+
         def body():
+            st = weak()
             x = st["latents"]  # [K, 4, F, h, w]: every variant's latent into its u_k and c_k chunk
             if do_cfg:
                 inp[nb - 2 * nvar:nb - nvar].copy_(x)
@@ -693,6 +765,8 @@ class I2VGenXLPipeline:
             saved_sc, u.source_chunks = u.source_chunks, smap
             saved_nv, u.variants = u.variants, nvar
             saved_pl, u.placement = u.placement, st["placement"]
+            saved_vp, u.variant_placements = u.variant_placements, st["variant_placements"]
+            saved_vm, u.variant_masks = u.variant_masks, None if st["vplace"] is None else st["vplace"]["masks"]
             try:
                 noise = u.forward_ext(inp, st["t"], mcond["fps"], mcond["image_latents_first"], mcond["image_latents"],
                                       mcond["image_embeddings"], mcond["encoder_hidden_states"], multi_frame_guidance=False,
@@ -700,10 +774,13 @@ class I2VGenXLPipeline:
             finally:
                 u.prune_source_tail, u.shared_prefix_chunks, u.source_chunks, u.variants = saved, saved_sp, saved_sc, saved_nv
                 u.placement = saved_pl
+                u.variant_placements, u.variant_masks = saved_vp, saved_vm
             # the engine's per-level offset tables are read by this state's captured graphs: they live as long as the state,
             # also after the engine drops its cache for another placement
             if st["placement"] is not None and not any(d is u._place_cache[1] for d in st["place_tables"]):
                 st["place_tables"].append(u._place_cache[1])
+            if st["variant_placements"] is not None and not any(d is u._vplace_cache[1] for d in st["place_tables"]):
+                st["place_tables"].append(u._vplace_cache[1])
             ops.ddim_step(x, noise[nb - nvar:nb].contiguous(), st["coef"],
                           v_uncond=noise[nb - 2 * nvar:nb - nvar].contiguous() if do_cfg else None, out=x)
 
@@ -715,13 +792,23 @@ class I2VGenXLPipeline:
         one conditioning class) share a chunk: the step's source map picks the batch."""
         if fuse is not None:
             mix, rnf, fobjs = fuse
-            for j, o in enumerate(fobjs):
+            vp = st["vplace"]
+            objs16 = [o.to(self.device, H16).contiguous() for o in fobjs] if vp is not None else None
+            for k in range(st["nvar"] if vp is not None else 0):
+                # per-variant placement: K launches of the shift and of the single-variant fusion entry on the variant's slice
+                # of the latents -- its object latents moved by ITS offsets, fused with ITS (moved) masks
+                for j, o in enumerate(objs16):
+                    ops.shift_planes(o, vp["place_dev"][k][j], out=st["fusion_objs"][j])
+                lat = st["latents"][k:k + 1]
+                ops.latent_fusion(lat, bg_latents, st["fusion_objs"], vp["fusion_masks"][k], mix, rnf, out=lat)
+            for j, o in enumerate(fobjs if vp is None else ()):
                 if st["place_dev"] is None:
                     st["fusion_objs"][j].copy_(o)
                 else:  # the object's inverted latents move with it (zero fill; the fusion masks are the shifted ones)
                     ops.shift_planes(o.to(self.device, H16).contiguous(), st["place_dev"][j], out=st["fusion_objs"][j])
-            ops.latent_fusion(st["latents"], bg_latents, st["fusion_objs"], st["fusion_masks"], mix, rnf, out=st["latents"],
-                              nvar=st["nvar"])
+            if vp is None:
+                ops.latent_fusion(st["latents"], bg_latents, st["fusion_objs"], st["fusion_masks"], mix, rnf, out=st["latents"],
+                                  nvar=st["nvar"])
             obj_latents = fobjs
         smap = plan_source_map(st.get("classes"), [bg_latents] + list(obj_latents))
         b = st["maps"].get(smap)
@@ -742,7 +829,8 @@ class I2VGenXLPipeline:
         u = self.unet
         vkey = (u.injection_masks(st["nvar"]), u.mask_key(st["masks"]), bool(u.pair_destinations), bool(u.prune_dead_chunks),
                 bool(self.prune_source_tail), bool(st.get("share_cfg_prefix")), smap, st["nvar"]) + \
-            (() if st["placement"] is None else (st["placement"],))
+            (() if st["placement"] is None else (st["placement"],)) + \
+            (() if st["variant_placements"] is None else ("variant_placements", st["variant_placements"]))
         g = st["variants"].get(vkey)
         if g is None:
             g = st["variants"][vkey] = GraphedStep(b["body"], preserve=(st["latents"],))
@@ -757,7 +845,8 @@ class I2VGenXLPipeline:
             negative_prompt_embeds=None, output_type="pil", return_dict=True, cross_attention_kwargs=None, clip_skip=1,
             fusion_steps=(0, 3), ddim_init_latents_t_idx=1, ddim_inv_prompt=None, obj_mask=None, obj_width_height=None,
             obj_ddim_latents_idx_offset=None, obj_random_noise_fusion=False, random_noise_ratio=0.0,
-            bg_inv_latents_path=None, obj_ddim_latents_path=None, obj_masks_tensors=None, obj_offsets=None):
+            bg_inv_latents_path=None, obj_ddim_latents_path=None, obj_masks_tensors=None, obj_offsets=None,
+            variant_obj_offsets=None):
         """PnP composition sampling.  ``obj_mask``: list of mask paths (preprocessed by ``mvoc_amd.utils.mask_preprocess``)
         or pass ``obj_masks_tensors`` = list of (float [1,4,F,h,w], bool [1,4,F,h,w]) directly.
 
@@ -769,7 +858,11 @@ class I2VGenXLPipeline:
 
         ``obj_offsets``: one entry per object, ``(dx, dy)`` or ``num_frames`` such pairs (a path), image pixels
         in multiples of 8 -- the object is composed that far from where it sits in its source clip (``normalize_obj_offsets``;
-        translation only, shared by the variants, not with a frame shard).  None or all zeros: exactly a call without it."""
+        translation only, shared by the variants, not with a frame shard).  None or all zeros: exactly a call without it.
+
+        ``variant_obj_offsets`` (not together with ``obj_offsets``): a list of K items, one per variant, each None
+        or a value ``obj_offsets`` accepts -- variant k composes the objects at ITS offsets over the one set of source chunks.
+        All items None / zero: exactly a call without it; all items equal: exactly the ``obj_offsets`` call."""
         from .utils import mask_preprocess
         # ---- the variants of this call (one with scalar arguments: the batch, kernels and launches of a single composition)
         m_rep = int(num_videos_per_prompt)
@@ -811,7 +904,17 @@ class I2VGenXLPipeline:
         c = self.conditioner
         n_obj = len(obj_ddim_latents_path)
         assert obj_mask is None or len(obj_mask) == n_obj
+        if obj_offsets is not None and variant_obj_offsets is not None:
+            raise ValueError("obj_offsets and variant_obj_offsets are both given: a call places its objects once for all "
+                             "variants or per variant")
         placement = normalize_obj_offsets(obj_offsets, n_obj, num_frames, self.vae_scale_factor)
+        variant_placements = None
+        if variant_obj_offsets is not None:
+            placement, variant_placements = resolve_variant_obj_offsets(variant_obj_offsets, nvar, n_obj, num_frames,
+                                                                        self.vae_scale_factor)
+        if variant_placements is not None and self.unet.shard is not None:
+            raise RuntimeError("variant_obj_offsets do not combine with the frame shard: the section masks are cut to pixel "
+                               "slabs and a shift crosses slabs")
         if placement is not None and self.unet.shard is not None:
             raise RuntimeError("obj_offsets do not combine with the frame shard: the section masks are cut to pixel slabs and a "
                                "shift crosses slabs")
@@ -897,7 +1000,8 @@ class I2VGenXLPipeline:
             obj_masks_tensors = [mask_preprocess(m, self.device, H16, 1, 4, num_frames, downscale=8) for m in obj_mask]
         self.unet.check_variant_schedules(nvar)  # per-variant injection schedules are hook state (pnp_utils): one entry per variant
         st = self.make_composition_state(latents, cond, obj_masks_tensors, scales if nvar > 1 else guidance_scale, variants=nvar,
-                                         **({} if placement is None else {"placement": placement}))
+                                         **({} if placement is None else {"placement": placement}),
+                                         **({} if variant_placements is None else {"variant_placements": variant_placements}))
         table, index = sched.coef_table(self.device, guidance_scale)
         if nvar > 1:  # [steps, K, 5]: a step's coefficient rows are one view, whatever K is
             table = torch.stack([sched.coef_table(self.device, g)[0] for g in scales], 1).contiguous()

@@ -359,7 +359,7 @@ class Transformer2DModel(_TransformerBase):
         if proc.injecting() and not eng._pruned:
             ndst, smap = eng.pnp_batch(B, proc.mask)
             active = eng.site_active(proc)
-            masks = eng.device_masks(proc.mask)[1]  # bool masks as {0,1} fp16
+            masks = eng.site_masks(eng.device_masks(proc.mask)[1], 1)  # bool masks as {0,1} fp16
             ld = qkv.stride(0)
             ops.pnp_blend_tokens(q, masks, x2=k, frames=F, height=H, width=W, channels=c, chunk_stride=F * hw * ld,
                                  f_stride=hw * ld, p_stride=ld, base_chunk0=proc.inject_background, ndst=ndst, src_map=smap,
@@ -452,7 +452,7 @@ class TransformerTemporalModel(_TransformerBase):
             q, k, v = qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:]
             if inject:
                 ndst, smap = eng.pnp_batch(B, proc.mask)
-                masks = eng.section_masks(proc.mask, 0, full_hw)  # soft float masks, channel 0
+                masks = eng.site_masks(eng.section_masks(proc.mask, 0, full_hw), 0)  # soft float masks, channel 0
                 ld = qkv.stride(0)
                 ops.pnp_blend_tokens(q, masks, x2=k, frames=F, height=H, width=W, channels=c, chunk_stride=F * hw * ld,
                                      f_stride=hw * ld, p_stride=ld, base_chunk0=proc.inject_background, ndst=ndst,
@@ -679,6 +679,15 @@ class I2VGenXLUNet:
         # by the composition loop, like source_chunks; shared by the variants.  Not with a frame shard.
         self.placement = None
         self._place_cache = (None, {})
+        # Per-variant placement (pipeline.py variant_obj_offsets): None, or a hashable tuple of K = ``variants``
+        # placements in the format of ``placement`` (a variant that is not placed carries all-zero offsets).  Every injection site
+        # then passes ``variant_masks`` -- (soft, hard) fp16 stacks [K, nobj, F, h, w] on the device, variant k's masks in ITS
+        # destination coordinates -- and the per-level [K, nobj, F, 2] table to the _placed_variants blend entries.  The hook mask
+        # lists still carry ONE mask set (shape checks and the mask key).  Set and restored around its forward by the composition
+        # loop, like placement; not together with placement, not with a frame shard.
+        self.variant_placements = None
+        self.variant_masks = None
+        self._vplace_cache = (None, {})
 
     def set_frame_shard(self, shard):
         """Frame-shard every forward over the ranks of ``shard`` (``mvoc_amd.frame_shard``): each rank receives the FULL
@@ -861,6 +870,8 @@ class I2VGenXLUNet:
     def place_table(self, mask_list, H, W):
         """the ``place=`` argument of a site's blend at H x W: None without a placement, else the device table of per-(object,
         frame) feature offsets, cached per (placement, H, W) and dropped when the placement changes"""
+        if self.variant_placements is not None:
+            return self.variant_place_table(mask_list, H, W)
         pl = self.placement
         if pl is None:
             return None
@@ -878,6 +889,46 @@ class I2VGenXLUNet:
             tab = self._place_cache[1][key] = ops.place_table(pl, H, W, mh, mw, self.device)
         return tab
 
+    def variant_place_table(self, mask_list, H, W):
+        """the ``place=`` argument under ``variant_placements``: the device table [K, nobj, F, 2] of this H x W, cached per
+        (variant_placements, H, W, mh, mw) and dropped when the placements change"""
+        vp = self.variant_placements
+        if self.placement is not None:
+            raise RuntimeError("variant_placements and placement are both set: a call places its objects per variant or once "
+                               "for all variants")
+        if self.shard is not None:
+            raise RuntimeError("variant_placements do not combine with the frame shard: the section masks are cut to pixel "
+                               "slabs and a shift crosses slabs")
+        if len(vp) != self.variants:
+            raise RuntimeError(f"variant_placements holds {len(vp)} placements, the call {self.variants} variants")
+        for k, pl in enumerate(vp):
+            if len(pl) != len(mask_list):
+                raise RuntimeError(f"variant_placements[{k}] holds offsets for {len(pl)} objects, the hooks carry "
+                                   f"{len(mask_list)} masks")
+        if self._vplace_cache[0] != vp:
+            self._vplace_cache = (vp, {})
+        mh, mw = self._all_frame_masks(mask_list)[0].shape[2:]
+        key = (H, W, mh, mw)
+        tab = self._vplace_cache[1].get(key)
+        if tab is None:
+            tab = self._vplace_cache[1][key] = ops.place_table_variants(vp, H, W, mh, mw, self.device)
+        return tab
+
+    def site_masks(self, masks, kind):
+        """the masks a site's blend reads (kind 0 = soft, 1 = hard): ``masks`` [nobj, F, h, w] of the hook state, or under
+        ``variant_placements`` the [K, nobj, F, h, w] stack of ``variant_masks`` (checked against the hook masks' shape)"""
+        if self.variant_placements is None:
+            return masks
+        vm = self.variant_masks
+        if vm is None:
+            raise RuntimeError("variant_placements is set but variant_masks is not: the engine needs the (soft, hard) "
+                               "[K, nobj, F, h, w] mask stacks of the placed variants")
+        stack = vm[kind]
+        if stack.dim() != 5 or stack.shape[0] != self.variants or tuple(stack.shape[1:]) != tuple(masks.shape):
+            raise RuntimeError(f"variant_masks[{kind}] is {tuple(stack.shape)}, expected [K = {self.variants}, "
+                               f"{', '.join(str(n) for n in masks.shape)}] (the hook masks per variant)")
+        return stack
+
     def place_kw(self, mask_list, H, W):
         """keyword arguments of a site's blend call: none without a placement (exactly today's call), else ``place=``"""
         tab = self.place_table(mask_list, H, W)
@@ -888,6 +939,9 @@ class I2VGenXLUNet:
         if self.placement is not None and self.shard is not None:
             raise RuntimeError("a placement does not combine with the frame shard: the section masks are cut to pixel slabs "
                                "and a shift crosses slabs")
+        if self.variant_placements is not None and self.shard is not None:
+            raise RuntimeError("variant_placements do not combine with the frame shard: the section masks are cut to pixel "
+                               "slabs and a shift crosses slabs")
         smap = self.pnp_src_map()
         if smap is not None and len(smap[1]) != len(mask_list):
             raise RuntimeError(f"source_chunks maps {len(smap[1])} objects, the hooks carry {len(mask_list)} masks")
@@ -986,6 +1040,7 @@ class I2VGenXLUNet:
             raise RuntimeError(f"feature injection needs masks at the feature resolution {(fh, fw)}, got "
                                f"{tuple(hard.shape[2:])} (reference: pnp_utils.py:994-1000 has no resize)")
         hard = self.section_masks(mask_list, 1, full_hw) if full_hw is not None else self.device_masks(mask_list)[1]
+        hard = self.site_masks(hard, 1)
         ld = h.stride(0)
         ops.pnp_blend_tokens(h, hard, frames=F, height=H, width=W, channels=channels, chunk_stride=F * H * W * ld,
                              f_stride=H * W * ld, p_stride=ld, base_chunk0=True, ndst=ndst, src_map=smap, nvar=self.variants,
@@ -1157,7 +1212,7 @@ class I2VGenXLUNet:
             self._pruned = False
         nchw = torch.empty((B * F, C, H, W), dtype=H16, device=self.device)
         nchw[:ns * F] = src.permute(0, 2, 1, 3, 4).reshape(ns * F, C, H, W)
-        ops.pnp_blend_nchw(nchw, self.device_masks(co.mask)[1], frames=F, base_chunk0=True, ndst=ndst, src_map=smap,
+        ops.pnp_blend_nchw(nchw, self.site_masks(self.device_masks(co.mask)[1], 1), frames=F, base_chunk0=True, ndst=ndst, src_map=smap,
                            nvar=self.variants, **self.place_kw(co.mask, H, W))  # (taken only when EVERY variant injects at conv_out)
         return nchw.reshape(B, F, C, H, W).permute(0, 2, 1, 3, 4).contiguous()
 
@@ -1280,7 +1335,7 @@ class I2VGenXLUNet:
             # so this tiny tensor goes through the NCHW form of the kernel on the boundary layout instead
             out = ops.tokens_to_ncfhw(y, B, co.cout, F, H, W)  # [B,C,F,h,w]
             nchw = out.permute(0, 2, 1, 3, 4).reshape(B * F, co.cout, H, W).contiguous()
-            ops.pnp_blend_nchw(nchw, self.device_masks(co.mask)[1], frames=F, base_chunk0=True, ndst=ndst, src_map=smap,
+            ops.pnp_blend_nchw(nchw, self.site_masks(self.device_masks(co.mask)[1], 1), frames=F, base_chunk0=True, ndst=ndst, src_map=smap,
                                nvar=self.variants, active=self.site_active(co), **self.place_kw(co.mask, H, W))
             out = nchw.reshape(B, F, co.cout, H, W).permute(0, 2, 1, 3, 4).contiguous()
         else:

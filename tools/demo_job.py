@@ -20,6 +20,9 @@ also runs the K compositions one by one in the same process and reports the rati
 --place "dx,dy;dx,dy" (opt-in): the entry's `obj_offset` (DESIGN.md 6k) -- one pair per object, image pixels in multiples of 8;
 the composition then places the objects that far from where they sit in their clips.  Reported like --variants (K = 1 unless
 --variants is given too).
+--variant-place "dx,dy;dx,dy|dx,dy;dx,dy|.." (opt-in, needs --variants K): K placements separated by `|`, each in the format of
+--place -- the variants' `placement` key: every variant composes the objects at its own offsets over the one set
+of source chunks.  With --sequential the K single jobs each take their variant's placement as `obj_offset`.
 
 --shared-source (opt-in): the shape of MVOC's own demo entries, where the background and both objects point at ONE inversion
 directory and the same control frames.  One clip is inverted, then the composition runs with source de-duplication off and then
@@ -367,7 +370,26 @@ def parse_place(text):
     return out
 
 
-def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, thresholds=None, sequential=False, place=None):
+def parse_variant_place(text, variants):
+    """"dx,dy;dx,dy|dx,dy;dx,dy" -> K placements, each as ``parse_place`` returns it (`|` separates the variants)"""
+    if not variants:
+        raise SystemExit("--variant-place needs --variants K (one placement per variant)")
+    items = text.split("|")
+    if len(items) != variants:
+        raise SystemExit(f"--variant-place {text!r}: {len(items)} placements for {variants} variants")
+    out = []
+    for k, item in enumerate(items):
+        try:
+            out.append(parse_place(item))
+        except SystemExit as e:
+            raise SystemExit(f"--variant-place, variant {k}: {e}")
+    if len({len(p) for p in out}) != 1:
+        raise SystemExit(f"--variant-place {text!r}: every variant needs one dx,dy per object")
+    return out
+
+
+def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, thresholds=None, sequential=False, place=None,
+                 variant_place=None):
     """K prompts and seeds over the boat_surf-shaped job (three distinct sources), one composition loop (composite.py `variants`).
     ``thresholds``: K values of pnp_spatial_attn_t, one per variant (the variants' `pnp` key); ``sequential``: after
     the one loop, the same K compositions one by one (single entries with the flat threshold) for the comparison."""
@@ -399,6 +421,11 @@ def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, threshol
     if thresholds is not None:
         for v, th in zip(var, thresholds):
             v["pnp"] = {"pnp_spatial_attn_t": float(th)}
+    if variant_place is not None:  # the variants' own placements
+        if len(variant_place) != variants:
+            raise SystemExit(f"--variant-place: {len(variant_place)} placements for {variants} variants")
+        for v, p in zip(var, variant_place):
+            v["placement"] = [list(q) for q in p]
     centry = dict(boat_surf_entry(size), variants=var)
     if place is not None:  # shared by the variants: an entry key
         centry["obj_offset"] = [list(p) for p in place]
@@ -414,15 +441,20 @@ def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, threshol
     dirs = sorted(files)
     if place is not None:
         res["obj_offset"] = [list(p) for p in place]
+    if variant_place is not None:
+        res["variant_placement"] = [[list(q) for q in p] for p in variant_place]
     if thresholds is not None:
         res["variant_thresholds"] = [float(t) for t in thresholds]
         res["output_suffix_of"] = {d: where[d] for d in dirs}
     if sequential:  # the K compositions one by one: single entries, the flat threshold key, the same prompts and seeds
         seq = []
         for k in range(variants):
-            e = dict(boat_surf_entry(size), edited_video_name=f"seq{k}", **{kk: vv for kk, vv in var[k].items() if kk != "pnp"})
+            e = dict(boat_surf_entry(size), edited_video_name=f"seq{k}",
+                     **{kk: vv for kk, vv in var[k].items() if kk not in ("pnp", "placement")})
             if place is not None:
                 e["obj_offset"] = [list(p) for p in place]
+            if variant_place is not None:  # the single job of variant k: its placement as the entry's
+                e["obj_offset"] = [list(q) for q in variant_place[k]]
             if thresholds is not None:
                 e["pnp_spatial_attn_t"] = float(thresholds[k])
             with StageTimer(pl) as t1:
@@ -460,12 +492,16 @@ if __name__ == "__main__":
                     help="with --variants K: also run the K compositions one by one and report the ratio")
     ap.add_argument("--place", type=str, default=None, metavar="dx,dy;dx,dy",
                     help="place the objects at composition time: one dx,dy per object, image pixels in multiples of 8 (`obj_offset`)")
+    ap.add_argument("--variant-place", type=str, default=None, metavar="dx,dy;dx,dy|..",
+                    help="with --variants K: K placements separated by |, each in the format of --place (the variants' `placement` key)")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
-    if a.variants or a.place:
+    if a.variants or a.place or a.variant_place:
         th = None if a.variant_thresholds is None else [float(x) for x in a.variant_thresholds.split(",")]
         place = None if a.place is None else parse_place(a.place)
-        print(json.dumps(run_variants(a.frames, a.size, a.steps, a.keep, a.variants or 1, th, a.sequential, place)), flush=True)
+        vplace = None if a.variant_place is None else parse_variant_place(a.variant_place, a.variants)
+        print(json.dumps(run_variants(a.frames, a.size, a.steps, a.keep, a.variants or 1, th, a.sequential, place, vplace)),
+              flush=True)
     else:
         fn = run_shared_source if a.shared_source else run
         print(json.dumps(fn(a.frames, a.size, a.steps, a.keep)), flush=True)
