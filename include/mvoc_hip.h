@@ -139,6 +139,12 @@ size_t mvoc_gemm_workspace_bytes(int64_t m, int64_t n, int64_t k);
  * pnp_utils.py:684-686, 862-864 and the stock AttnProcessor2_0 sites).
  * q/k/v/out element (b, t, h, d) lives at base + b*bs + t*ts + h*head_dim + d  (elements).
  * kv batch index = b / kv_bdiv (cross-attention context shared by all frames of a sample).
+ * The descriptor describes exactly the elements (b, t, h, d) with b < nbatch (b / kv_bdiv for k / v / v2), t < tq (q, out, out2) or
+ * t < tk (k, v, v2), h < heads, d < head_dim: elements outside these extents (padding rows behind a batch entry's last row, columns
+ * of a row beyond heads * head_dim, whatever follows the last row) never influence a result, whatever they hold, and no byte of
+ * out / out2 outside the described extents is written.  (tests/test_attention_contract_gpu.py fills them with NaN / a sentinel.)
+ * The fields from head_dim on are optional: a caller that does not use them must leave them ZERO (zero-initialise the whole
+ * descriptor, e.g. `mvoc_attn_desc d = {0};`): an uninitialised head_dim / causal / scale / v2 / out2 / pipelined is read as a request.
  * ------------------------------------------------------------------------------------------- */
 typedef struct mvoc_attn_desc {
   const void *q, *k, *v;
@@ -165,7 +171,11 @@ typedef struct mvoc_attn_desc {
 /* spatial self-attention and image/text cross-attention (flash-style, K/V tiles LDS-staged) */
 int mvoc_flash_attn_f16(const mvoc_attn_desc* d, void* stream);
 /* temporal self-attention: one sequence per (sample, pixel), tq == tk == frames <= 32; "t" walks frames
- * (ts = H*W*C for the canonical layout), "b" walks sample*pixel via (b / hw)*bs + (b % hw)*ps */
+ * (ts = H*W*C for the canonical layout), "b" walks sample*pixel via (b / hw)*bs + (b % hw)*ps.
+ * Described are the elements (sample < nsample, pixel < hw, frame < frames, h < heads, d < 64) of each operand: elements outside
+ * these extents (padding pixels, frames or columns between them, whatever follows the last) never influence a result, whatever they
+ * hold, and no byte of out outside the described extents is written.  Every field is required; a descriptor that grows trailing
+ * optional fields is to be zero-initialised as a whole (`mvoc_tattn_desc d = {0};`), as for mvoc_attn_desc. */
 typedef struct mvoc_tattn_desc {
   const void *q, *k, *v;
   void* out;

@@ -716,10 +716,11 @@ def test_flash_attn_kernels_agree_bitwise(ops, nb, heads, tq, tk, kv_bdiv, pair)
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
 
 
-@pytest.mark.parametrize("frames,heads", [(16, 2), (3, 1), (32, 1), (8, 5)])
-def test_temporal_attn(ops, frames, heads):
+@pytest.mark.parametrize("frames,heads,hw", [pytest.param(f, h, 21, id=f"{f}-{h}") for f, h in ((16, 2), (3, 1), (32, 1), (8, 5))] +
+                         [(f, h, hw) for hw in (1, 4) for f, h in ((16, 2), (3, 1), (32, 1), (8, 5))])  # hw 1 / 4: below / at one 32-row tile's pixels
+def test_temporal_attn(ops, frames, heads, hw):
     g = torch.Generator().manual_seed(frames)
-    ns, hw = 3, 21
+    ns = 3
     c = heads * 64
     qkv = torch.randn(ns * frames * hw, 3 * c, generator=g).half()
     d = dev(qkv)
