@@ -302,6 +302,13 @@ typedef struct mvoc_pnp_desc {
   const void* masks;
   int64_t chunk_stride, f_stride, p_stride;
   int32_t nobj, frames, height, width, channels, mask_h, mask_w, base_chunk0;
+  /* base_chunk0: 0 = the base is the last chunk, 1 = the base is chunk 0 (the layouts above).  -1 = NO BACKGROUND CHUNK:
+     the tensors hold [obj_1..obj_k, (uncond,) cond] -- object j (counted from 0) is chunk j, the chunk count is k + ndst and the
+     base is the last chunk; arithmetic and object order are unchanged, so the destination rows are bit-identical to base_chunk0 = 0
+     on the layout with a background chunk in front (which that blend never reads).  Taken by the positional
+     mvoc_pnp_blend_scatter_tokens only: every _nchw entry and every entry that takes a map returns -1 with an error text and
+     launches nothing (a map expresses the layout already: nsrc = k, obj_chunk[j] = j, base_chunk0 = 0; the feature blends of
+     the _nchw entries need chunk 0).  A zero-initialised descriptor means what it always meant. */
   int32_t ndst;  /* trailing destination chunks: 0 or 2 = [uncond, cond] (the reference's layout), 1 = [cond] only: the
                     classifier-free-guidance-off batch [bg, obj_1..obj_k, cond] (n = k + 2) */
 } mvoc_pnp_desc;

@@ -22,18 +22,21 @@ struct PnpArgs {
   // scalar, not an array: the run-time object loop indexes it with a shift (a run-time-indexed array member risks scratch)
   int nsrc;
   unsigned obj_map;
+  // (positional kernels) 1: the batch has no background chunk, [obj_1..obj_n, (uncond,) cond] -- object j is chunk j, the base
+  // the last chunk (mvoc_pnp_desc.base_chunk0 = -1; base_chunk0 is 0 here)
+  int no_background;
 };
 
 template <bool MAPPED>
 __device__ __forceinline__ int obj_chunk(const PnpArgs& p, int j) {
   if constexpr (MAPPED) return (int)((p.obj_map >> (4 * j)) & 15u);
-  return j + 1;
+  return p.no_background ? j : j + 1;
 }
 
 template <bool MAPPED>
 __device__ __forceinline__ int chunk_count(const PnpArgs& p) {
   if constexpr (MAPPED) return p.nsrc + p.ndst;
-  return p.nobj + 1 + p.ndst;
+  return p.nobj + (p.no_background ? 0 : 1) + p.ndst;
 }
 
 __device__ __forceinline__ float blend16(float inj, float obj, float m) {
@@ -661,6 +664,16 @@ int fill_args(const mvoc_pnp_desc* d, PnpArgs& a) {
   a.sx = (float)d->mask_w / (float)d->width;
   a.nsrc = d->nobj + 1;
   a.obj_map = 0;
+  a.no_background = 0;
+  return 0;
+}
+
+// base_chunk0 = -1 (no background chunk) is the positional tokens entry's alone: every other entry refuses it before it launches anything (a map
+// expresses that layout already: nsrc = nobj, obj_chunk[j] = j; an _nchw entry blends features onto chunk 0, which is not there)
+int refuse_no_background(const mvoc_pnp_desc* d, const char* entry) {
+  MVOC_REQUIRE(!d || d->base_chunk0 != -1, -1,
+               "%s: base_chunk0 = -1 (no background chunk) is taken by mvoc_pnp_blend_scatter_tokens only (a mapped entry expresses "
+               "the layout as nsrc = nobj, obj_chunk[j] = j; the nchw entries need chunk 0)", entry);
   return 0;
 }
 
@@ -830,6 +843,7 @@ void launch_nchw_variants_n(bool vec, dim3 grid, hipStream_t s, const PnpArgs& a
 
 extern "C" int mvoc_pnp_blend_scatter_tokens_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
                                                       int32_t nvar, void* stream) {
+  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_tokens_variants")) return rc;
   PnpArgs a;
   double chunks = 0;
   if (int rc = fill_variants(d, nsrc, obj_chunk, nvar, a, chunks)) return rc;
@@ -854,6 +868,7 @@ extern "C" int mvoc_pnp_blend_scatter_tokens_variants(const mvoc_pnp_desc* d, in
 
 extern "C" int mvoc_pnp_blend_scatter_nchw_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
                                                     int32_t nvar, void* stream) {
+  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_nchw_variants")) return rc;
   PnpArgs a;
   double chunks = 0;
   if (int rc = fill_variants(d, nsrc, obj_chunk, nvar, a, chunks)) return rc;
@@ -904,6 +919,7 @@ void launch_nchw_variants_sel_n(bool vec, dim3 grid, hipStream_t s, const PnpArg
 
 extern "C" int mvoc_pnp_blend_scatter_tokens_variants_sel(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
                                                           int32_t nvar, uint32_t active, void* stream) {
+  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_tokens_variants_sel")) return rc;
   PnpArgs a;
   double chunks = 0;
   if (int rc = fill_variants_sel(d, nsrc, obj_chunk, nvar, active, a, chunks)) return rc;
@@ -929,6 +945,7 @@ extern "C" int mvoc_pnp_blend_scatter_tokens_variants_sel(const mvoc_pnp_desc* d
 
 extern "C" int mvoc_pnp_blend_scatter_nchw_variants_sel(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
                                                         int32_t nvar, uint32_t active, void* stream) {
+  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_nchw_variants_sel")) return rc;
   PnpArgs a;
   double chunks = 0;
   if (int rc = fill_variants_sel(d, nsrc, obj_chunk, nvar, active, a, chunks)) return rc;
@@ -972,6 +989,7 @@ void launch_nchw_placed_n(bool vec, dim3 grid, hipStream_t s, const PnpArgs& a, 
 
 extern "C" int mvoc_pnp_blend_scatter_tokens_placed(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
                                                     uint32_t active, const int32_t* place, void* stream) {
+  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_tokens_placed")) return rc;
   PnpArgs a;
   double chunks = 0;
   if (int rc = fill_placed(d, nsrc, obj_chunk, nvar, active, place, a, chunks)) return rc;
@@ -998,6 +1016,7 @@ extern "C" int mvoc_pnp_blend_scatter_tokens_placed(const mvoc_pnp_desc* d, int3
 
 extern "C" int mvoc_pnp_blend_scatter_nchw_placed(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
                                                   uint32_t active, const int32_t* place, void* stream) {
+  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_nchw_placed")) return rc;
   PnpArgs a;
   double chunks = 0;
   if (int rc = fill_placed(d, nsrc, obj_chunk, nvar, active, place, a, chunks)) return rc;
@@ -1050,6 +1069,7 @@ void launch_nchw_placed_variants_n(bool vec, dim3 grid, hipStream_t s, const Pnp
 
 extern "C" int mvoc_pnp_blend_scatter_tokens_placed_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
                                                              int32_t nvar, uint32_t active, const int32_t* place, void* stream) {
+  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_tokens_placed_variants")) return rc;
   PnpArgs a;
   double chunks = 0;
   int on = 0;
@@ -1079,6 +1099,7 @@ extern "C" int mvoc_pnp_blend_scatter_tokens_placed_variants(const mvoc_pnp_desc
 
 extern "C" int mvoc_pnp_blend_scatter_nchw_placed_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
                                                            int32_t nvar, uint32_t active, const int32_t* place, void* stream) {
+  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_nchw_placed_variants")) return rc;
   PnpArgs a;
   double chunks = 0;
   int on = 0;
@@ -1149,10 +1170,16 @@ extern "C" int mvoc_latent_fusion_variants_f16(const void* latents, const void* 
 extern "C" int mvoc_pnp_blend_scatter_tokens(const mvoc_pnp_desc* d, void* stream) {
   PnpArgs a;
   if (int rc = fill_args(d, a)) return rc;
+  if (d->base_chunk0 == -1) {  // no background chunk: the base is the last chunk, as with base_chunk0 = 0
+    a.no_background = 1;
+    a.base_chunk0 = 0;
+  }
+  // chunks read: nobj objects + the base (chunk 0, or the last chunk) -- the same count in both layouts
   return launch_tokens<false>(d, a, d->nobj + 1, stream);
 }
 
 extern "C" int mvoc_pnp_blend_scatter_nchw(const mvoc_pnp_desc* d, void* stream) {
+  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_nchw")) return rc;
   PnpArgs a;
   if (int rc = fill_args(d, a)) return rc;
   return launch_nchw<false>(d, a, d->nobj + 1, stream);
@@ -1160,6 +1187,7 @@ extern "C" int mvoc_pnp_blend_scatter_nchw(const mvoc_pnp_desc* d, void* stream)
 
 extern "C" int mvoc_pnp_blend_scatter_tokens_mapped(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
                                                     void* stream) {
+  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_tokens_mapped")) return rc;
   PnpArgs a;
   int nread = 0;
   if (int rc = fill_args(d, a)) return rc;
@@ -1169,6 +1197,7 @@ extern "C" int mvoc_pnp_blend_scatter_tokens_mapped(const mvoc_pnp_desc* d, int3
 
 extern "C" int mvoc_pnp_blend_scatter_nchw_mapped(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
                                                   void* stream) {
+  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_nchw_mapped")) return rc;
   PnpArgs a;
   int nread = 0;
   if (int rc = fill_args(d, a)) return rc;

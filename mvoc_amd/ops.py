@@ -64,7 +64,9 @@ def _gemm(d: GemmDesc, dev=None, out=None, sums=False, rowmom=False):
             if hasattr(out, attr):
                 delattr(out, attr)
     d.concurrency = _CONCURRENCY.n
-    if sums and out is not None and d.m % 256 == 0 and d.act == ACT_NONE and out.is_contiguous() and out.shape[1] == d.n_store:
+    # (whether this SITE asks for the statistics does not depend on the row count: the host query below is then asked at every batch)
+    want_sums = sums and out is not None and d.act == ACT_NONE and out.is_contiguous() and out.shape[1] == d.n_store
+    if want_sums and d.m % 256 == 0:
         # REQUEST for the producer-epilogue GroupNorm statistics (include/mvoc_hip.h: chan_sums); honoured by the eight-phase tiles
         cs = torch.empty((d.m // 256, out.shape[1], 2), dtype=torch.float32, device=out.device)
         d.chan_sums = cs.data_ptr()
@@ -75,7 +77,7 @@ def _gemm(d: GemmDesc, dev=None, out=None, sums=False, rowmom=False):
         rm = torch.empty((d.m, ld, 2), dtype=torch.float32, device=out.device)
         d.row_moments, d.row_moments_ld = rm.data_ptr(), ld
     check(lib.mvoc_gemm_f16(C.byref(d), _stream()), "gemm")
-    if cs is not None and lib.mvoc_gemm_chan_sums_written():
+    if want_sums and lib.mvoc_gemm_chan_sums_written() and cs is not None:
         out.chan_sums = cs  # rides on the tensor OBJECT: a view / slice / copy of it carries no statistics
     if rm is not None:
         w_ = lib.mvoc_gemm_row_moments_written()
@@ -548,16 +550,28 @@ def _active_mask(active, nvar, what):
 
 
 def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride, f_stride, p_stride, x2=None,
-                     base_chunk0=False, ndst=2, src_map=None, nvar=1, active=None, place=None):
+                     base_chunk0=False, ndst=2, src_map=None, nvar=1, active=None, place=None, no_background=False):
     """In-place masked blend + scatter on channel-contiguous data (see include/mvoc_hip.h).  ``ndst``: trailing
     destination chunks (2 = [uncond, cond], 1 = [cond] with CFG off).  ``src_map`` = (nsrc, obj_chunks): the batch holds
     nsrc de-duplicated source chunks, object j reads chunk obj_chunks[j] (None: [bg, obj_1..obj_n], the unmapped entry).
     ``nvar`` = K > 1: K variants share the sources, the batch is [s.., u_1..u_K, c_1..c_K] ([s.., c_1..c_K] with ndst 1).
     ``active``: bit k set = variant k injects (None or all K bits: every variant, the entries of a call without it).
     ``place``: the table of ``place_table`` for this height x width: every object is read at its shifted pixel,
-    ``masks`` are in destination coordinates -- the ``_placed`` entry, whatever ``nvar`` / ``src_map`` / ``active`` are."""
+    ``masks`` are in destination coordinates -- the ``_placed`` entry, whatever ``nvar`` / ``src_map`` / ``active`` are.
+    ``no_background``: the batch is [obj_1..obj_n, (uncond,) cond] with no background chunk in front -- the
+    positional entry only: not with ``base_chunk0``, a map, variants or a placement (a map (nobj, range(nobj)) says the same
+    there)."""
     d = _pnp_desc(x, x2, masks, chunk_stride, f_stride, p_stride, frames, height, width, channels, base_chunk0, ndst)
     active = _active_mask(active, nvar, "pnp_blend_tokens")
+    if no_background:
+        if base_chunk0:
+            raise RuntimeError("pnp_blend_tokens: no_background with base_chunk0: the base would be the chunk the batch does not hold")
+        if src_map is not None or nvar != 1 or place is not None or active is not None:
+            raise RuntimeError("pnp_blend_tokens: no_background is the positional entry's flag; with a source map, variants or a "
+                               "placement pass src_map=(nobj, range(nobj)) instead")
+        last = (d.nobj + (int(ndst) or 2) - 1) * chunk_stride
+        _check_variants(x, x2, 1, last + (frames - 1) * f_stride + (height * width - 1) * p_stride + channels, "pnp_blend_tokens")
+        d.base_chunk0 = -1  # (include/mvoc_hip.h: no background chunk, the base is the last chunk)
     if masks.dim() == 5 and (place is None or place.dim() != 4):
         raise RuntimeError("pnp_blend_tokens: a [K, nobj, F, mh, mw] mask stack needs place= as an int32 [K, nobj, F, 2] table")
     if nvar != 1 or place is not None:

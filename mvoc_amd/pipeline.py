@@ -311,6 +311,9 @@ class I2VGenXLPipeline:
         self._streams = []
         # composition loop: the UNet's source chunks are never read behind the last injection site (unet.prune_source_tail)
         self.prune_source_tail = os.environ.get("MVOC_PRUNE_SOURCE_TAIL", "1") != "0"  # (=0: A/B)
+        # ... and on a step where only Q/K sites registered with inject_background=False inject, nothing reads the background chunk
+        # either: the UNet runs without it (unet.prune_background)
+        self.prune_background = os.environ.get("MVOC_PRUNE_BACKGROUND", "1") != "0"  # (=0: A/B)
         # ... and its unconditional / conditional chunks are one computation up to the first cross-attention (unet.shared_prefix_chunks)
         self.share_cfg_prefix = os.environ.get("MVOC_SHARE_CFG_PREFIX", "1") != "0"  # (=0: A/B)
         # ... and source roles that are the same source (same conditioning, same inversion latents) share one chunk: the batch
@@ -761,6 +764,7 @@ class I2VGenXLPipeline:
             inp[nb - nvar:].copy_(x)
             u = self.unet
             saved, u.prune_source_tail = u.prune_source_tail, bool(self.prune_source_tail)  # this loop reads the destination chunks only
+            saved_pb, u.prune_background = u.prune_background, bool(self.prune_background)  # ... and never the background's output
             saved_sp, u.shared_prefix_chunks = u.shared_prefix_chunks, (2 if st["share_cfg_prefix"] else 0)
             saved_sc, u.source_chunks = u.source_chunks, smap
             saved_nv, u.variants = u.variants, nvar
@@ -775,6 +779,7 @@ class I2VGenXLPipeline:
                 u.prune_source_tail, u.shared_prefix_chunks, u.source_chunks, u.variants = saved, saved_sp, saved_sc, saved_nv
                 u.placement = saved_pl
                 u.variant_placements, u.variant_masks = saved_vp, saved_vm
+                u.prune_background = saved_pb
             # the engine's per-level offset tables are read by this state's captured graphs: they live as long as the state,
             # also after the engine drops its cache for another placement
             if st["placement"] is not None and not any(d is u._place_cache[1] for d in st["place_tables"]):
@@ -785,6 +790,27 @@ class I2VGenXLPipeline:
                           v_uncond=noise[nb - 2 * nvar:nb - nvar].contiguous() if do_cfg else None, out=x)
 
         return {"inp": inp, "cond": mcond, "prepared": prepared, "body": body, "nb": nb}
+
+    def background_dead(self, smap):
+        """whether the UNet drops the background chunk on the step the CURRENT hook state describes, run on the batch of source
+        map ``smap`` (``unet.background_dead`` as the iteration body will see it: the body sets both attributes)"""
+        u = self.unet
+        saved = u.prune_background, u.source_chunks
+        u.prune_background, u.source_chunks = bool(self.prune_background), smap
+        try:
+            return bool(u.background_dead())
+        finally:
+            u.prune_background, u.source_chunks = saved
+
+    def composition_variant_key(self, st, smap):
+        """what a captured composition iteration bakes in, as the key of ``st["variants"]`` (see ``composition_step``).  A run
+        alternates steps that drop the background chunk and steps that need it: each kind has its own graph"""
+        u = self.unet
+        return (u.injection_masks(st["nvar"]), u.mask_key(st["masks"]), bool(u.pair_destinations), bool(u.prune_dead_chunks),
+                bool(self.prune_source_tail), bool(st.get("share_cfg_prefix")), smap, st["nvar"]) + \
+            (() if st["placement"] is None else (st["placement"],)) + \
+            (() if st["variant_placements"] is None else ("variant_placements", st["variant_placements"])) + \
+            (("no_background",) if self.background_dead(smap) else ())
 
     def composition_step(self, st, t, bg_latents, obj_latents, table_row, fuse=None):
         """one iteration of ``:1636-1734`` on device-resident latents; ``fuse`` = (mix_ratio, obj_random_noise_fusion,
@@ -826,11 +852,7 @@ class I2VGenXLPipeline:
         # a captured iteration bakes in EVERY site's injecting decision (the reference allows a schedule per site; with
         # per-variant schedules, DESIGN.md 6j, a site's decision is the bitmask of its injecting variants -- 0 or all bits
         # without them), the device copies of the masks and the batch's source map: all are part of the variant key
-        u = self.unet
-        vkey = (u.injection_masks(st["nvar"]), u.mask_key(st["masks"]), bool(u.pair_destinations), bool(u.prune_dead_chunks),
-                bool(self.prune_source_tail), bool(st.get("share_cfg_prefix")), smap, st["nvar"]) + \
-            (() if st["placement"] is None else (st["placement"],)) + \
-            (() if st["variant_placements"] is None else ("variant_placements", st["variant_placements"]))
+        vkey = self.composition_variant_key(st, smap)
         g = st["variants"].get(vkey)
         if g is None:
             g = st["variants"][vkey] = GraphedStep(b["body"], preserve=(st["latents"],))

@@ -363,7 +363,7 @@ class Transformer2DModel(_TransformerBase):
             ld = qkv.stride(0)
             ops.pnp_blend_tokens(q, masks, x2=k, frames=F, height=H, width=W, channels=c, chunk_stride=F * hw * ld,
                                  f_stride=hw * ld, p_stride=ld, base_chunk0=proc.inject_background, ndst=ndst, src_map=smap,
-                                 nvar=eng.variants, active=active, **eng.place_kw(proc.mask, H, W))
+                                 nvar=eng.variants, active=active, **eng.no_background_kw(smap), **eng.place_kw(proc.mask, H, W))
         if ndst == 2 and eng.pair_destinations and active is not None:
             # per-variant schedules: only the variants whose q / k were just overwritten attend with u_k's q, k
             # equal to c_k's.  Per maximal run of equal activity: an injecting run [k0, k1) is one paired launch (its u and c
@@ -457,7 +457,7 @@ class TransformerTemporalModel(_TransformerBase):
                 ops.pnp_blend_tokens(q, masks, x2=k, frames=F, height=H, width=W, channels=c, chunk_stride=F * hw * ld,
                                      f_stride=hw * ld, p_stride=ld, base_chunk0=proc.inject_background, ndst=ndst,
                                      src_map=smap, nvar=eng.variants, active=eng.site_active(proc),
-                                     **eng.place_kw(proc.mask, H, W))
+                                     **eng.no_background_kw(smap), **eng.place_kw(proc.mask, H, W))
                 if eng._tail_site is self:  # (prune_source_tail) the last reader of the source chunks was this blend
                     r0 = (B - ndst * eng.variants) * F * hw
                     q, k, v, h, x = q[r0:], k[r0:], v[r0:], h[r0:], x[r0:]
@@ -648,6 +648,15 @@ class I2VGenXLUNet:
         # pipeline.py, which never reads those chunks, turns it on.
         self.prune_source_tail = False
         self._tail_site = None
+        # The BACKGROUND chunk (chunk 0) is read by the feature injections (resnet / temporal conv / conv_out: base = chunk 0) and by
+        # a Q/K blend registered with inject_background=True.  On a step where only Q/K sites with inject_background=False inject
+        # (pnp_utils.py:633-641, 786-794: base = the conditional chunk, objects = chunks 1..n; 45 of the demo's 50 steps) nothing
+        # reads it, and the loop around the UNet reads the destination chunks only: with prune_background such a forward
+        # (``background_dead``) runs rows [1:] of the batch -- [obj_1..obj_n, (uncond,) cond] -- and returns chunk 0 zero-filled,
+        # the way prune_source_tail returns the source chunks.  Off by default (forward_ext stays faithful chunk
+        # by chunk); the composition loop of pipeline.py turns it on.  Every other forward is unchanged.
+        self.prune_background = False
+        self._no_bg = False
         # Classifier-free guidance feeds the SAME latent, image latents, fps and timestep to the unconditional and the conditional
         # chunk (pipeline_i2vgen_xl.py:1676-1690); they differ in the prompt / CLIP-image embeddings, which enter through the
         # spatial transformers' cross-attention only.  Up to the first cross-attention (conv_in, transformer_in, the first
@@ -828,12 +837,23 @@ class I2VGenXLUNet:
 
     # ---- PnP helpers ------------------------------------------------------------------------------
     @staticmethod
-    def check_pnp_batch(B, mask_list, nsrc=None, variants=1):
+    def check_pnp_batch(B, mask_list, nsrc=None, variants=1, no_background=False):
         """the hooks address chunks positionally [bg, obj_1..obj_n, uncond, cond] (pnp_utils.py:592 hard-codes 5); with
         classifier-free guidance off the batch is [bg, obj_1..obj_n, cond].  ``nsrc``: the number of source
         chunks of a source-de-duplicated batch (``source_chunks``; None = n_objects + 1).  Returns the number of trailing
         destination chunks (2 or 1).  ``variants`` = K > 1: the batch carries K destination
-        pairs (or K conditional chunks) behind the sources, B = nsrc + ndst * K; the return value stays the chunks PER variant."""
+        pairs (or K conditional chunks) behind the sources, B = nsrc + ndst * K; the return value stays the chunks PER variant.
+        ``no_background`` (a forward that ``prune_background`` runs without chunk 0): the sources are the object chunks alone,
+        B = n_objects + ndst * K (``nsrc``, when given, counts the chunks that are left)."""
+        if no_background:
+            ns = nsrc if nsrc is not None else (None if mask_list is None else len(mask_list))
+            if not 1 <= variants <= 8:
+                raise RuntimeError(f"variants = {variants}: 1 to 8 variants share one set of source chunks")
+            if ns is None or B - ns not in (variants, 2 * variants):
+                raise RuntimeError(f"PnP injection is active but the UNet batch is {B}: without its background chunk "
+                                   f"(prune_background) the batch is the {ns} object chunks + {2 * variants} destination chunks "
+                                   f"([obj.., u_1..u_{variants}, c_1..c_{variants}]) or + {variants} with guidance off")
+            return (B - ns) // variants
         if variants != 1:
             ns = nsrc if nsrc is not None else (None if mask_list is None else len(mask_list) + 1)
             if not 1 <= variants <= 8:
@@ -950,7 +970,40 @@ class I2VGenXLUNet:
                 raise RuntimeError("variants > 1 do not combine with the frame shard: run one composition per call")
             if self.shared_prefix_chunks:
                 raise RuntimeError("variants > 1 do not combine with shared_prefix_chunks (DESIGN.md 6i)")
+        if self._no_bg:
+            # this forward runs without chunk 0 (background_dead): every chunk number is one lower.  The positional batch with one
+            # variant and no placement stays on the positional entry (its no_background flag); every other call passes the
+            # renumbered map to the entry it takes anyway
+            nsrc = (len(mask_list) if smap is None else smap[0] - 1)
+            chunks = tuple(range(nsrc)) if smap is None else tuple(c - 1 for c in smap[1])
+            ndst = self.check_pnp_batch(B, mask_list, nsrc, self.variants, no_background=True)
+            positional = smap is None and self.variants == 1 and self.placement is None and self.variant_placements is None
+            return ndst, (None if positional else (nsrc, chunks))
         return self.check_pnp_batch(B, mask_list, None if smap is None else smap[0], self.variants), smap
+
+    def no_background_kw(self, smap):
+        """keyword arguments of a Q/K site's blend call: none on a forward that holds chunk 0 (exactly today's call), else the
+        positional entry's ``no_background`` flag -- unless ``pnp_batch`` returned the renumbered map, which says the same"""
+        return {"no_background": True} if self._no_bg and smap is None else {}
+
+    def background_dead(self):
+        """True when nothing reads chunk 0 of the forward the CURRENT hook state describes (``prune_background``):
+        (a) at least one attention site injects, (b) every attention site that injects (in any variant) has inject_background
+        False, (c) no resnet / temporal-conv / conv_out site injects (in any variant): those blend onto chunk 0, (d) under
+        ``source_chunks`` no object maps to chunk 0, (e) no frame shard"""
+        if not self.prune_background or self._pruned or self.shard is not None:
+            return False
+        attn = False
+        for s in self.hook_sites():
+            if not s.injecting():
+                continue
+            if not isinstance(s, Processor) or s.inject_background:
+                return False
+            attn = True
+        sc = self.source_chunks
+        if sc is not None and any(int(c) == 0 for c in sc[1]):
+            return False
+        return attn
 
     def device_masks(self, mask_list):
         """list of (float [1,4,F,h,w], bool [1,4,F,h,w]) pairs (``register_time_all``'s ``mask``) ->
@@ -1033,6 +1086,7 @@ class I2VGenXLUNet:
         ``full_hw`` is given by temporal sections (see ``section_masks``); elsewhere the rows are whole local frames.
         ``site``: the calling hook site (its per-variant schedules pick the variants that are written)."""
         B, F, H, W = geo
+        assert not self._no_bg, "a feature injection blends onto chunk 0: background_dead() is False on such a forward"
         ndst, smap = self.pnp_batch(B, mask_list)
         hard = self._all_frame_masks(mask_list)[1]
         fh, fw = full_hw if full_hw is not None else (H, W)
@@ -1226,6 +1280,7 @@ class I2VGenXLUNet:
             return self._forward_impl(*args, **kw)
         finally:
             self._tall = None  # the batched time projection belongs to this call only (a resnet run on its own recomputes it)
+            self._no_bg = False
 
     def _forward_impl(self, sample, timestep, fps, image_latents_first, image_latents, image_embeddings, encoder_hidden_states,
                       multi_frame_guidance, conditioning=None):
@@ -1249,9 +1304,29 @@ class I2VGenXLUNet:
         B_full = B
         up_factor = 2 ** self.num_upsamplers
         forward_upsample_size = any(s % up_factor != 0 for s in (H, W))
-        temb_act = self._embeddings(timestep, fps, B)
-        self._tall = self.time_proj_all(temb_act)
+        temb_act = self._embeddings(timestep, fps, B)  # (per chunk of the CALL's batch: B rows of 320 numbers)
         sh = self.shard
+        if conditioning is not None and conditioning.key != ((B, C, F, H, W), bool(multi_frame_guidance), id(sh)):
+            raise RuntimeError(f"conditioning was prepared for {conditioning.key}, this call is "
+                               f"{((B, C, F, H, W), bool(multi_frame_guidance), id(sh))}")
+        if self.background_dead():
+            # prune_background: nothing reads chunk 0 on this forward -- the network runs rows [1:] of the sample and of every
+            # conditioning tensor (slices of the hoisted set: views, no copies) and chunk 0 of the result is zeros (below)
+            self._no_bg = True
+            rows = lambda t: t[1:] if torch.is_tensor(t) and t.dim() > 0 and t.shape[0] == B_full else t
+            sample, temb_act = sample[1:], temb_act[1:]
+            image_latents_first, image_latents = rows(image_latents_first), rows(image_latents)
+            image_embeddings, encoder_hidden_states = rows(image_embeddings), rows(encoder_hidden_states)
+            B = B_full - 1
+            if conditioning is not None:
+                c0 = conditioning.ctx
+                per = c0.tokens.shape[0] // B_full
+                ctx = Context(c0.tokens[per:], c0.length, c0.frames_per_ctx)
+                ctx.kv = {k: v[per:] for k, v in c0.kv.items()}
+                ctx.keep = c0.keep
+                conditioning = Conditioning(ctx, conditioning.stem8[F * hw:], (B, F, H, W), conditioning.frames,
+                                            ((B, C, F, H, W), bool(multi_frame_guidance), id(sh)))
+        self._tall = self.time_proj_all(temb_act)
         if conditioning is None:
             conditioning = self._conditioning((B, C, F, H, W), image_latents_first, image_latents, image_embeddings,
                                               encoder_hidden_states, multi_frame_guidance)
