@@ -232,6 +232,14 @@ int mvoc_temporal_qkv_attn_f16(const mvoc_tfused_desc* d, void* stream);
  * statistics per image), :188 and TemporalConvLayer (5-D, statistics per video), :430, and
  * pipeline_i2vgen_xl.py:351-352.  Input may be a 2-source channel concat.  Deterministic (no atomics).
  *   workspace floats: nsample * (nchunk*3 + 2) * groups  -> mvoc_groupnorm_workspace_bytes
+ * Extents (every entry of this family, mvoc_row_stats_f16, mvoc_layernorm_f16 and mvoc_row_stats_from_moments_f32 included;
+ * enforced by tests/test_norm_contract_gpu.py on allocations whose undescribed elements are NaN):
+ *   - only the elements [nsample * rows_per_sample][c1] of x and [..][c - c1] of x2 influence a result; likewise only the
+ *     described extents of gamma, beta, chan_sums(2), parts and moments, and of a moments row of stride ld only its
+ *     ceil(n / tile_w) tile entries;
+ *   - no byte of out, stats, moments or wp_sets outside its extent is written;
+ *   - no byte of the workspace beyond mvoc_groupnorm_workspace_bytes(...) is written;
+ *   - the workspace's prior contents never influence a result.
  * ------------------------------------------------------------------------------------------- */
 typedef struct mvoc_gn_desc {
   const void* x;        /* [nsample*rows_per_sample][c1] fp16 */

@@ -304,6 +304,16 @@ __global__ __launch_bounds__(256) void gn_apply(const GnArgs p) {
 }
 
 
+// W'[row][col] = fl16(fl32(W (gamma rstd))): ONE definition for the stored weight and for the mean term of the constant.  The empty asm pins
+// the fp32 rounding of the product: without it hipcc fused product and conversion into v_fma_mixlo_f16 (ONE rounding) in the constants loop
+// only, so where the fp32 product sits on an fp16 tie (1 element in ~8 000) the constant was built from the fp16 neighbour of the weight the
+// consumer multiplies -- an error of ulp16(W') |mean| that the rounded-weight form below exists to exclude
+__device__ __forceinline__ half_t gn_fold_weight(float w, float g, float rstd) {
+  float p = w * (g * rstd);
+  asm("" : "+v"(p));
+  return (half_t)p;
+}
+
 // GroupNorm folded into the LINEAR that reads it (GN -> proj_in of the two transformer kinds: pnp_utils.py:185-191, 433-438 --
 // no activation in between): y = W (gamma (x - mean) rstd + beta) + b = (W gamma rstd) x + (b + W (beta - gamma mean rstd)).  Per
 // SAMPLE (mean / rstd are per sample and group) this kernel writes the scaled weights W'_s, in mvoc_xs_linear_f16's packed
@@ -324,7 +334,7 @@ __global__ __launch_bounds__(256) void gn_fold_xs_kernel(const GnArgs p, const h
     const half8_t gv = *reinterpret_cast<const half8_t*>(p.gamma + col);
     half8_t o;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (half_t)((float)wv[e] * ((float)gv[e] * fin[2 * ((col + e) / p.cpg) + 1]));
+    for (int e = 0; e < 8; ++e) o[e] = gn_fold_weight((float)wv[e], (float)gv[e], fin[2 * ((col + e) / p.cpg) + 1]);
     *reinterpret_cast<half8_t*>(out + (long)q * 8) = o;
   }
   // constants: 8 threads per row, each a fixed eighth of the columns, summed in lane order
@@ -340,7 +350,7 @@ __global__ __launch_bounds__(256) void gn_fold_xs_kernel(const GnArgs p, const h
       // the mean term from the weight AS ROUNDED above (the consumer computes sum fl16(W') x + c'): then y = sum W' (x - mean) + W beta
       // + b and the rounding error of W' scales with |x - mean|, not with |mean| (a group whose mean is many sigma off zero)
       const float* f = fin + 2 * ((col + e) / p.cpg);
-      const float wr = (float)(half_t)((float)wv[e] * ((float)gv[e] * f[1]));
+      const float wr = (float)gn_fold_weight((float)wv[e], (float)gv[e], f[1]);
       acc += (float)wv[e] * (float)bv[e] - wr * f[0];
     }
   }
