@@ -13,6 +13,9 @@ thresholds of its own.  An entry's ``obj_offset: [[dx, dy], ...]`` (one item per
 pixels in multiples of 8) places the objects at composition time (``placement_kwargs``; shared by the entry's variants).
 A variant's ``placement: [[dx, dy], ...]`` (the format of ``obj_offset``) places the objects for that variant alone
 (``variant_placement_kwargs``); a variant without the key takes the entry's ``obj_offset``, or none.
+An entry's ``obj_transform: [{offset, scale, flip, anchor}, ...]`` (one dict per object, every key optional) scales, mirrors and
+places the objects at composition time (``transform_kwargs``; shared by the entry's variants, not with ``obj_offset`` or a
+variant's ``placement``).
 """
 import argparse
 import json
@@ -155,6 +158,26 @@ def variant_placement_kwargs(config, variants):
                                     for c in variants]}
 
 
+def transform_kwargs(config, variants=None):
+    """the entry's optional ``obj_transform`` (one dict per object: ``offset``, ``scale``, ``flip``, ``anchor``)
+    with the placements of ``variant_placement_kwargs``: none of the keys -> {} (exactly today's call); ``obj_transform`` alone
+    -> ``obj_transforms`` as plain dicts and lists (the call checks and normalises them; shared by the entry's variants: not one
+    of ``VARIANT_KEYS``); together with ``obj_offset`` or any variant's ``placement`` it is an error -- a transform carries its
+    own offset.  ``obj_width_height`` stays ignored, as in the reference."""
+    if "obj_transform" not in config or config.obj_transform is None:
+        return variant_placement_kwargs(config, variants)
+    if "obj_offset" in config and config.obj_offset is not None:
+        raise ValueError("obj_transform and obj_offset are both set: put the offset into the transform ('offset')")
+    if variants is not None and any("placement" in c and c.placement is not None for c in variants):
+        raise ValueError("obj_transform is set and a variant sets 'placement': one transform serves all variants of an entry")
+
+    def plain(v):
+        if hasattr(v, "keys"):
+            return {str(k): plain(v[k]) for k in v.keys()}
+        return [plain(x) for x in v] if hasattr(v, "__iter__") and not isinstance(v, (str, bytes)) else v
+    return {"obj_transforms": plain(config.obj_transform)}
+
+
 def variant_output_dir(config, k):
     """``<output_dir>/<output_suffix of the variant's merged config>/variant_{k:02d}``"""
     return os.path.join(config.output_dir, output_suffix(config), f"variant_{k:02d}")
@@ -201,7 +224,7 @@ def main(template_config, configs_list, device, synthetic=False, dedup_sources=F
                   obj_ddim_latents_path=config.obj_ddim_latents_path,
                   obj_ddim_latents_idx_offset=config.obj_ddim_latents_idx_offset,
                   obj_random_noise_fusion=config.obj_random_noise_fusion, fusion_steps=config.fusion_step,
-                  **variant_placement_kwargs(config, variants))
+                  **transform_kwargs(config, variants))
         if variants is None:
             output_dirs, configs = [os.path.join(config.output_dir, output_suffix(config))], [config]
         else:  # K variants in one loop: per-variant prompt / negative prompt / seed / cfg / main image, everything else shared

@@ -397,6 +397,31 @@ int mvoc_pnp_blend_scatter_nchw_placed_variants(const mvoc_pnp_desc* d, int32_t 
  * [4, F, h, w] latents (nplane = 4).  Every int32 offset is valid. */
 int mvoc_shift_planes_f16(const void* src, void* dst, int32_t nplane, int32_t frames, int32_t h, int32_t w,
                           const int32_t* offsets, void* stream);
+/* Scale and mirror: the _placed entries with a nearest-neighbour GATHER in place of the shift.  `maps` is a DEVICE
+ * table of int32 [nobj][frames][height + width]: row (j * frames + f) holds ymap (height entries) and then xmap (width entries)
+ * of object j in frame f on THIS call's height x width grid; the caller owns it and keeps it unchanged for as long as a captured
+ * graph may replay the launch.  For destination pixel (py, px) of frame f object j contributes the vector of its chunk at pixel
+ * (ymap[py], xmap[px]) of frame f and the mask value masks[j][f][nearest(py)][nearest(px)] -- the masks are given in DESTINATION
+ * coordinates (mvoc_gather_planes_f16 moves them there) and sampled at the destination pixel as above.  An entry outside
+ * [0, height) / [0, width) -- -1 by convention, but EVERY int32 value is safe: the entries are compared unsigned and the source
+ * pixel is formed in 64 bits -- means the object is absent there: value 0 and mask 0 enter the same three fp16-rounded ops
+ * (nothing is skipped: a -0.0 base becomes +0.0 as under a zero mask).  Object order, ndst, base_chunk0, the source map, nvar and
+ * `active` are those of _placed.  The destination rows are bit-identical to the entries above on object chunks gathered with
+ * zero fill and masks zeroed where a map entry is outside; maps ymap[y] = y - dfy, xmap[x] = x - dfx are the _placed entry with
+ * the table (dfy, dfx), identity maps the _variants_sel entry.  Bytes counted per launch (MvocProfScope): those of _placed
+ * + 4 * nobj*frames*(height + width) for the table.  The table's contents are on the device and are not read by the host.
+ * Requires a non-NULL table, 1 <= nvar <= 8, 1 <= active < (1u << nvar), a valid map and base_chunk0 != -1 (else -1 and an error
+ * text, nothing written). */
+int mvoc_pnp_blend_scatter_tokens_resampled(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
+                                            uint32_t active, const int32_t* maps, void* stream);
+int mvoc_pnp_blend_scatter_nchw_resampled(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
+                                          uint32_t active, const int32_t* maps, void* stream);
+/* Zero-filled per-frame gather of contiguous fp16 planes [nplane][frames][h][w] (src != dst):
+ *     dst[pl][f][y][x] = src[pl][f][ymap_f[y]][xmap_f[x]], or 0 where either index lies outside the plane
+ * `maps`: DEVICE int32 [frames][h + w], ymap_f (h entries) and then xmap_f (w entries), shared by the nplane planes (the planes
+ * of one call belong to one object, as for mvoc_shift_planes_f16).  Every int32 entry is valid (compared unsigned). */
+int mvoc_gather_planes_f16(const void* src, void* dst, int32_t nplane, int32_t frames, int32_t h, int32_t w,
+                           const int32_t* maps, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Loop glue on [B,4,F,h,w] fp16 latents, BIT-EXACT vs the reference's eager fp16 op chain.

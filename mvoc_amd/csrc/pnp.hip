@@ -630,6 +630,162 @@ __global__ __launch_bounds__(256) void pnp_nchw_placed_variants_kernel(const Pnp
   }
 }
 
+// ---- scale and mirror: nearest resampling through per-axis index maps ---------------------------------------
+// The _placed kernels with a gather in place of the shift: object j of frame f is read at the pixel (ymap[py], xmap[px]), the
+// maps taken from row j * frames + f of maps = int32 [nobj][frames][height + width] (ymap first, then xmap) -- a device table
+// for THIS site's H x W, constant for the whole call.  The kernels cannot see who wrote the table: an entry is compared UNSIGNED
+// against height / width, anything outside (every negative value included) means the object is absent there, and the source pixel
+// is formed in 64 bits.  Absent = value 0 and mask 0 entering blend16_h, as in the _placed kernels; the masks are in destination
+// coordinates and sampled at the destination pixel.  Kernels of their own, so the instantiations above compile as they always did.
+__device__ __forceinline__ bool resampled_src(const int* __restrict__ maps, int j, int frames, int f, int py, int px, int h, int w,
+                                              long& spix) {
+  const int* mp = maps + ((long)j * frames + f) * ((long)h + w);
+  const unsigned sy = (unsigned)mp[py], sx = (unsigned)mp[h + px];
+  spix = (long)sy * w + sx;
+  return sy < (unsigned)h && sx < (unsigned)w;
+}
+
+template <int NOBJ>
+__global__ __launch_bounds__(256) void pnp_tokens_resampled_kernel(const PnpArgs p, const int nvar, const unsigned active,
+                                                                   const int* __restrict__ maps) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= p.total) return;
+  half_t* x = p.x[blockIdx.y];
+  const int c8n = p.channels >> 3;
+  const int c8 = (int)(idx % c8n);
+  const long fp = idx / c8n;
+  const int hw = p.height * p.width;
+  const int f = (int)(fp / hw), px = (int)(fp % hw);
+  const int py = px / p.width, pxx = px - py * p.width;
+  const int my = nearest_src(py, p.sy, p.mask_h), mx = nearest_src(pxx, p.sx, p.mask_w);
+  const long foff = (long)f * p.f_stride + c8 * 8;
+  const long off = foff + (long)px * p.p_stride;
+  half8_t ov[NOBJ];
+  half_t m[NOBJ];
+#pragma unroll
+  for (int j = 0; j < NOBJ; ++j) {
+    long spix;
+    const bool in = resampled_src(maps, j, p.frames, f, py, pxx, p.height, p.width, spix);
+    m[j] = (half_t)0.0f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) ov[j][e] = (half_t)0.0f;
+    if (in) {
+      m[j] = p.masks[(((long)j * p.frames + f) * p.mask_h + my) * p.mask_w + mx];
+      ov[j] = *reinterpret_cast<const half8_t*>(x + obj_chunk<true>(p, j) * p.chunk_stride + foff + spix * p.p_stride);
+    }
+  }
+  half8_t o;
+  if (p.base_chunk0) {  // one blend for every injecting variant
+    const half8_t bv = *reinterpret_cast<const half8_t*>(x + off);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      half_t inj = bv[e];
+#pragma unroll
+      for (int j = 0; j < NOBJ; ++j) inj = blend16_h(inj, ov[j][e], m[j]);
+      o[e] = inj;
+    }
+  }
+  for (int k = 0; k < nvar; ++k) {
+    if (!((active >> k) & 1u)) continue;
+    half_t* cond = x + var_dst(p, nvar, p.ndst - 1, k) * p.chunk_stride + off;
+    if (!p.base_chunk0) {
+      const half8_t bv = *reinterpret_cast<const half8_t*>(cond);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        half_t inj = bv[e];
+#pragma unroll
+        for (int j = 0; j < NOBJ; ++j) inj = blend16_h(inj, ov[j][e], m[j]);
+        o[e] = inj;
+      }
+    }
+    if (p.ndst == 2) *reinterpret_cast<half8_t*>(x + var_dst(p, nvar, 0, k) * p.chunk_stride + off) = o;
+    *reinterpret_cast<half8_t*>(cond) = o;
+  }
+}
+
+// NCHW: object values one pixel at a time (each of the VEC pixels of a work item has its own source pixel, and under a scale
+// neighbouring destinations no longer read neighbouring sources); base and destinations vectorised when VEC == 8
+template <int VEC, int NOBJ>
+__global__ __launch_bounds__(256) void pnp_nchw_resampled_kernel(const PnpArgs p, const int nvar, const unsigned active,
+                                                                 const int* __restrict__ maps) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= p.total) return;
+  half_t* x = p.x[blockIdx.y];
+  const int hw = p.height * p.width;
+  const int pvn = hw / VEC;
+  const int pv = (int)(idx % pvn);
+  const long fc = idx / pvn;
+  const int f = (int)(fc / p.channels);
+  const long off = fc * hw + (long)pv * VEC;  // (f*C + c)*HW + p
+  const long chunk = (long)p.frames * p.channels * hw;
+  half_t ov[NOBJ][VEC];
+  half_t m[NOBJ][VEC];
+#pragma unroll
+  for (int j = 0; j < NOBJ; ++j) {
+    const half_t* src = x + obj_chunk<true>(p, j) * chunk + fc * hw;
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      const int px = pv * VEC + e;
+      const int py = px / p.width, pxx = px - py * p.width;
+      long spix;
+      const bool in = resampled_src(maps, j, p.frames, f, py, pxx, p.height, p.width, spix);
+      m[j][e] = (half_t)0.0f;
+      ov[j][e] = (half_t)0.0f;
+      if (in) {
+        const int my = nearest_src(py, p.sy, p.mask_h), mx = nearest_src(pxx, p.sx, p.mask_w);
+        m[j][e] = p.masks[(((long)j * p.frames + f) * p.mask_h + my) * p.mask_w + mx];
+        ov[j][e] = src[spix];
+      }
+    }
+  }
+  half_t tmp[VEC];
+  if (p.base_chunk0) {
+    ld_vec<VEC>(tmp, x + off);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      half_t inj = tmp[e];
+#pragma unroll
+      for (int j = 0; j < NOBJ; ++j) inj = blend16_h(inj, ov[j][e], m[j][e]);
+      tmp[e] = inj;
+    }
+  }
+  for (int k = 0; k < nvar; ++k) {
+    if (!((active >> k) & 1u)) continue;
+    half_t* cond = x + var_dst(p, nvar, p.ndst - 1, k) * chunk + off;
+    if (!p.base_chunk0) {
+      ld_vec<VEC>(tmp, cond);
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        half_t inj = tmp[e];
+#pragma unroll
+        for (int j = 0; j < NOBJ; ++j) inj = blend16_h(inj, ov[j][e], m[j][e]);
+        tmp[e] = inj;
+      }
+    }
+    if (p.ndst == 2) st_vec<VEC>(x + var_dst(p, nvar, 0, k) * chunk + off, tmp);
+    st_vec<VEC>(cond, tmp);
+  }
+}
+
+// zero-filled per-frame gather of [nplane][F][h][w]: dst[pl, f, y, x] = src[pl, f, ymap_f[y], xmap_f[x]] or 0 where either
+// index is outside the plane (compared unsigned: every int32 entry is safe); maps = F rows of h + w int32 (ymap, then xmap) on
+// the device, shared by the planes
+__global__ __launch_bounds__(256) void gather_planes_kernel(const half_t* __restrict__ src, half_t* __restrict__ dst, int frames,
+                                                            int h, int w, const int* __restrict__ maps, long n) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int xx = (int)(i % w);
+  const long r = i / w;
+  const int y = (int)(r % h);
+  const long pf = r / h;  // pl * frames + f
+  const int f = (int)(pf % frames);
+  const int* mp = maps + (long)f * ((long)h + w);
+  const unsigned sy = (unsigned)mp[y], sx = (unsigned)mp[h + xx];
+  half_t v = (half_t)0.0f;
+  if (sy < (unsigned)h && sx < (unsigned)w) v = src[(pf * h + sy) * w + sx];
+  dst[i] = v;
+}
+
 // zero-filled per-frame integer translation of [nplane][F][h][w]: dst[pl, f, y, x] = src[pl, f, y - dy_f, x - dx_f] or 0;
 // offsets = F int32 pairs (dy_f, dx_f) on the device, shared by the planes
 __global__ __launch_bounds__(256) void shift_planes_kernel(const half_t* __restrict__ src, half_t* __restrict__ dst, int frames,
@@ -1123,6 +1279,97 @@ extern "C" int mvoc_pnp_blend_scatter_nchw_placed_variants(const mvoc_pnp_desc* 
     default: launch_nchw_placed_variants_n<4>(vec, grid, s, a, nvar, active, pl); break;
   }
   return mvoc_check_launch("pnp_nchw_placed_variants_kernel");
+}
+
+namespace {
+
+// _resampled: the _placed contract with the table of per-axis index maps in place of the offset table
+int fill_resampled(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar, uint32_t active, const void* maps,
+                   PnpArgs& a, double& chunks) {
+  MVOC_REQUIRE(maps, -1, "pnp resampled: null map table");
+  return fill_variants_sel(d, nsrc, obj_chunk, nvar, active, a, chunks);
+}
+
+template <int NOBJ>
+void launch_nchw_resampled_n(bool vec, dim3 grid, hipStream_t s, const PnpArgs& a, int nvar, unsigned active, const int* maps) {
+  if (vec)
+    hipLaunchKernelGGL((pnp_nchw_resampled_kernel<8, NOBJ>), grid, dim3(256), 0, s, a, nvar, active, maps);
+  else
+    hipLaunchKernelGGL((pnp_nchw_resampled_kernel<1, NOBJ>), grid, dim3(256), 0, s, a, nvar, active, maps);
+}
+
+}  // namespace
+
+extern "C" int mvoc_pnp_blend_scatter_tokens_resampled(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
+                                                       uint32_t active, const int32_t* maps, void* stream) {
+  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_tokens_resampled")) return rc;
+  PnpArgs a;
+  double chunks = 0;
+  if (int rc = fill_resampled(d, nsrc, obj_chunk, nvar, active, maps, a, chunks)) return rc;
+  MVOC_REQUIRE(d->channels % 8 == 0 && d->chunk_stride % 8 == 0 && d->f_stride % 8 == 0 && d->p_stride % 8 == 0, -2,
+               "pnp tokens: channels/strides must be multiples of 8");
+  a.total = (long)d->frames * d->height * d->width * (d->channels / 8);
+  const long nblk = (a.total + 255) / 256;
+  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "pnp tokens: grid too large");
+  const int ntens = d->x2 ? 2 : 1;
+  hipStream_t s = (hipStream_t)stream;
+  const double elems = (double)d->frames * d->height * d->width * d->channels;
+  MvocProfScope prof(MVOC_FAM_PNP, s,
+                     ntens * (elems * 2.0 * chunks + 2.0 * d->nobj * d->frames * d->height * d->width) +
+                         4.0 * d->nobj * d->frames * ((double)d->height + d->width));
+  const dim3 grid((unsigned)nblk, ntens);
+  const unsigned act = active;
+  const int* mp = (const int*)maps;
+  switch (d->nobj) {
+    case 1: hipLaunchKernelGGL(pnp_tokens_resampled_kernel<1>, grid, dim3(256), 0, s, a, (int)nvar, act, mp); break;
+    case 2: hipLaunchKernelGGL(pnp_tokens_resampled_kernel<2>, grid, dim3(256), 0, s, a, (int)nvar, act, mp); break;
+    case 3: hipLaunchKernelGGL(pnp_tokens_resampled_kernel<3>, grid, dim3(256), 0, s, a, (int)nvar, act, mp); break;
+    default: hipLaunchKernelGGL(pnp_tokens_resampled_kernel<4>, grid, dim3(256), 0, s, a, (int)nvar, act, mp); break;
+  }
+  return mvoc_check_launch("pnp_tokens_resampled_kernel");
+}
+
+extern "C" int mvoc_pnp_blend_scatter_nchw_resampled(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
+                                                     uint32_t active, const int32_t* maps, void* stream) {
+  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_nchw_resampled")) return rc;
+  PnpArgs a;
+  double chunks = 0;
+  if (int rc = fill_resampled(d, nsrc, obj_chunk, nvar, active, maps, a, chunks)) return rc;
+  const long hw = (long)d->height * d->width;
+  const bool vec = hw % 8 == 0;
+  a.total = (long)d->frames * d->channels * (vec ? hw / 8 : hw);
+  const long nblk = (a.total + 255) / 256;
+  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "pnp nchw: grid too large");
+  const int ntens = d->x2 ? 2 : 1;
+  hipStream_t s = (hipStream_t)stream;
+  const double elems = (double)d->frames * hw * d->channels;
+  MvocProfScope prof(MVOC_FAM_PNP, s,
+                     ntens * (elems * 2.0 * chunks + 2.0 * d->nobj * d->frames * hw) +
+                         4.0 * d->nobj * d->frames * ((double)d->height + d->width));
+  const dim3 grid((unsigned)nblk, ntens);
+  const int* mp = (const int*)maps;
+  switch (d->nobj) {
+    case 1: launch_nchw_resampled_n<1>(vec, grid, s, a, nvar, active, mp); break;
+    case 2: launch_nchw_resampled_n<2>(vec, grid, s, a, nvar, active, mp); break;
+    case 3: launch_nchw_resampled_n<3>(vec, grid, s, a, nvar, active, mp); break;
+    default: launch_nchw_resampled_n<4>(vec, grid, s, a, nvar, active, mp); break;
+  }
+  return mvoc_check_launch("pnp_nchw_resampled_kernel");
+}
+
+extern "C" int mvoc_gather_planes_f16(const void* src, void* dst, int32_t nplane, int32_t frames, int32_t h, int32_t w,
+                                      const int32_t* maps, void* stream) {
+  MVOC_REQUIRE(src && dst && maps, -1, "gather_planes: null operand");
+  MVOC_REQUIRE(src != dst, -1, "gather_planes: in place (src == dst) is not supported");
+  MVOC_REQUIRE(nplane > 0 && frames > 0 && h > 0 && w > 0, -1, "gather_planes: bad dims");
+  const long n = (long)nplane * frames * h * w;
+  const long nblk = (n + 255) / 256;
+  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "gather_planes: grid too large");
+  hipStream_t s = (hipStream_t)stream;
+  MvocProfScope prof(MVOC_FAM_MISC, s, 2.0 * n * 2 + 4.0 * frames * ((double)h + w));
+  hipLaunchKernelGGL(gather_planes_kernel, dim3((unsigned)nblk), dim3(256), 0, s, (const half_t*)src, (half_t*)dst, (int)frames,
+                     (int)h, (int)w, (const int*)maps, n);
+  return mvoc_check_launch("gather_planes_kernel");
 }
 
 extern "C" int mvoc_shift_planes_f16(const void* src, void* dst, int32_t nplane, int32_t frames, int32_t h, int32_t w,

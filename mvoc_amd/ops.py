@@ -550,7 +550,7 @@ def _active_mask(active, nvar, what):
 
 
 def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride, f_stride, p_stride, x2=None,
-                     base_chunk0=False, ndst=2, src_map=None, nvar=1, active=None, place=None, no_background=False):
+                     base_chunk0=False, ndst=2, src_map=None, nvar=1, active=None, place=None, no_background=False, resample=None):
     """In-place masked blend + scatter on channel-contiguous data (see include/mvoc_hip.h).  ``ndst``: trailing
     destination chunks (2 = [uncond, cond], 1 = [cond] with CFG off).  ``src_map`` = (nsrc, obj_chunks): the batch holds
     nsrc de-duplicated source chunks, object j reads chunk obj_chunks[j] (None: [bg, obj_1..obj_n], the unmapped entry).
@@ -560,7 +560,12 @@ def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride,
     ``masks`` are in destination coordinates -- the ``_placed`` entry, whatever ``nvar`` / ``src_map`` / ``active`` are.
     ``no_background``: the batch is [obj_1..obj_n, (uncond,) cond] with no background chunk in front -- the
     positional entry only: not with ``base_chunk0``, a map, variants or a placement (a map (nobj, range(nobj)) says the same
-    there)."""
+    there).
+    ``resample``: the table of ``resample_table`` for this height x width: every object is read at the pixel its
+    per-axis maps name (scale, mirror and translation, nearest), ``masks`` are in destination coordinates -- the ``_resampled``
+    entry, whatever ``nvar`` / ``src_map`` / ``active`` are.  Not with ``place``, not with a per-variant mask stack."""
+    if resample is not None:
+        _refuse_resample_mix(place, masks, no_background, "pnp_blend_tokens")
     d = _pnp_desc(x, x2, masks, chunk_stride, f_stride, p_stride, frames, height, width, channels, base_chunk0, ndst)
     active = _active_mask(active, nvar, "pnp_blend_tokens")
     if no_background:
@@ -574,11 +579,16 @@ def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride,
         d.base_chunk0 = -1  # (include/mvoc_hip.h: no background chunk, the base is the last chunk)
     if masks.dim() == 5 and (place is None or place.dim() != 4):
         raise RuntimeError("pnp_blend_tokens: a [K, nobj, F, mh, mw] mask stack needs place= as an int32 [K, nobj, F, 2] table")
-    if nvar != 1 or place is not None:
+    if nvar != 1 or place is not None or resample is not None:
         nsrc, chunks = _variant_map(src_map, d.nobj)
         last = (nsrc + (int(ndst) or 2) * int(nvar) - 1) * chunk_stride
         _check_variants(x, x2, nvar, last + (frames - 1) * f_stride + (height * width - 1) * p_stride + channels,
                         "pnp_blend_tokens")
+        if resample is not None:
+            _check_resample(resample, d.nobj, frames, height, width, "pnp_blend_tokens")
+            check(lib.mvoc_pnp_blend_scatter_tokens_resampled(C.byref(d), nsrc, chunks, int(nvar), _all_or(active, nvar),
+                                                              resample.data_ptr(), _stream()), "pnp_blend_scatter_tokens_resampled")
+            return x
         if _check_place_variants(place, masks, nvar, d.nobj, frames, "pnp_blend_tokens"):
             check(lib.mvoc_pnp_blend_scatter_tokens_placed_variants(C.byref(d), nsrc, chunks, int(nvar), _all_or(active, nvar),
                                                                     place.data_ptr(), _stream()),
@@ -603,19 +613,27 @@ def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride,
     return x
 
 
-def pnp_blend_nchw(x, masks, *, frames, x2=None, base_chunk0=True, ndst=2, src_map=None, nvar=1, active=None, place=None):
+def pnp_blend_nchw(x, masks, *, frames, x2=None, base_chunk0=True, ndst=2, src_map=None, nvar=1, active=None, place=None,
+                   resample=None):
     """In-place on x [(nobj+1+ndst)*F, C, H, W] (reference feature-map layout); with ``src_map`` = (nsrc, obj_chunks)
     x is [(nsrc+ndst)*F, C, H, W], with ``nvar`` = K > 1 [(nsrc+ndst*K)*F, C, H, W]; ``active`` picks the variants that are
-    written, ``place`` moves the objects (see ``pnp_blend_tokens``)."""
+    written, ``place`` moves the objects, ``resample`` scales / mirrors / moves them (see ``pnp_blend_tokens``)."""
     if x.dim() != 4 or not x.is_contiguous():
         raise RuntimeError("pnp_blend_nchw: x must be contiguous [N, C, H, W]")
+    if resample is not None:
+        _refuse_resample_mix(place, masks, False, "pnp_blend_nchw")
     d = _pnp_desc(x, x2, masks, 0, 0, 0, frames, x.shape[2], x.shape[3], x.shape[1], base_chunk0, ndst)
     active = _active_mask(active, nvar, "pnp_blend_nchw")
     if masks.dim() == 5 and (place is None or place.dim() != 4):
         raise RuntimeError("pnp_blend_nchw: a [K, nobj, F, mh, mw] mask stack needs place= as an int32 [K, nobj, F, 2] table")
-    if nvar != 1 or place is not None:
+    if nvar != 1 or place is not None or resample is not None:
         nsrc, chunks = _variant_map(src_map, d.nobj)
         _check_variants(x, x2, nvar, (nsrc + (int(ndst) or 2) * int(nvar)) * frames * x[0].numel(), "pnp_blend_nchw")
+        if resample is not None:
+            _check_resample(resample, d.nobj, frames, x.shape[2], x.shape[3], "pnp_blend_nchw")
+            check(lib.mvoc_pnp_blend_scatter_nchw_resampled(C.byref(d), nsrc, chunks, int(nvar), _all_or(active, nvar),
+                                                            resample.data_ptr(), _stream()), "pnp_blend_scatter_nchw_resampled")
+            return x
         if _check_place_variants(place, masks, nvar, d.nobj, frames, "pnp_blend_nchw"):
             check(lib.mvoc_pnp_blend_scatter_nchw_placed_variants(C.byref(d), nsrc, chunks, int(nvar), _all_or(active, nvar),
                                                                   place.data_ptr(), _stream()),
@@ -726,6 +744,86 @@ def shift_planes(src, offsets, out=None):
         raise RuntimeError("shift_planes: out must be contiguous and of src's shape")
     check(lib.mvoc_shift_planes_f16(src.data_ptr(), out.data_ptr(), src.numel() // (frames * h * w), frames, h, w, offsets.data_ptr(),
                                     _stream()), "shift_planes")
+    return out
+
+
+# ---- scale and mirror: nearest resampling through per-axis index maps ---------------------------------------
+def level_axis_map(d, p, q, flip, a2, size, mask_size):
+    """the source index of every destination index of ONE axis of a feature grid of ``size`` rows under a latent (mask) axis of
+    ``mask_size`` rows -> a list of ``size`` ints, -1 where the object is absent.  The object appears ``p / q`` times its source
+    size, mirrored when ``flip``, about the anchor ``a2`` / 2 (latent rows; pixel i has its centre at i + 1/2), then moved by
+    ``d`` latent rows (``level_offset`` carries d to this level).  Python ints only: floor of the exact rational, which is nearest
+    on pixel centres.  p == q without a flip is ``i - level_offset(d)``: the translation of DESIGN.md 6k."""
+    d, p, q, a2, S, L = int(d), int(p), int(q), int(a2), int(size), int(mask_size)
+    if p < 1 or q < 1 or S < 1 or L < 1:
+        raise RuntimeError(f"level_axis_map: scale {p}/{q} and the sizes {S}, {L} must be positive")
+    sg = -1 if flip else 1
+    df = level_offset(d, S, L)
+    out = []
+    for i in range(S):
+        num = a2 * S * p + sg * q * ((2 * (i - df) + 1) * L - a2 * S)
+        s = num // (2 * p * L)
+        out.append(s if 0 <= s < S else -1)
+    return out
+
+
+def transform_maps(transform, height, width, mask_h, mask_w):
+    """``transform`` = per object (py, qy, px, qx, flip_y, flip_x, ay2, ax2, ((dy, dx) per frame)) -> nested lists
+    [nobj][F][height + width]: per frame ``level_axis_map`` of the y axis, then of the x axis"""
+    if not transform or len({len(t[8]) for t in transform}) != 1 or not transform[0][8]:
+        raise RuntimeError("transform_maps: every object needs the same number (>= 1) of per-frame offsets")
+    rows = []
+    for py, qy, px, qx, fy, fx, ay2, ax2, offs in transform:
+        ycache, xcache = {}, {}
+        obj = []
+        for dy, dx in offs:
+            if dy not in ycache:
+                ycache[dy] = level_axis_map(dy, py, qy, fy, ay2, height, mask_h)
+            if dx not in xcache:
+                xcache[dx] = level_axis_map(dx, px, qx, fx, ax2, width, mask_w)
+            obj.append(ycache[dy] + xcache[dx])
+        rows.append(obj)
+    return rows
+
+
+def resample_table(transform, height, width, mask_h, mask_w, device):
+    """the device table the ``_resampled`` blend entries read: int32 [nobj, F, height + width] (``transform_maps``).  Every
+    entry is in [-1, size) by construction; the kernels treat any other value as absent as well"""
+    return torch.tensor(transform_maps(transform, height, width, mask_h, mask_w), dtype=torch.int32).to(device).contiguous()
+
+
+def _refuse_resample_mix(place, masks, no_background, what):
+    if place is not None:
+        raise RuntimeError(f"{what}: resample= and place= are both given: a translation is part of the resample table")
+    if masks.dim() == 5:
+        raise RuntimeError(f"{what}: resample= does not take a [K, nobj, F, mh, mw] mask stack: one transform serves all variants")
+    if no_background:
+        raise RuntimeError(f"{what}: resample= with no_background: pass src_map=(nobj, range(nobj)) instead")
+
+
+def _check_resample(maps, nobj, frames, height, width, what):
+    _chk(maps, "resample", torch.int32)
+    if tuple(maps.shape) != (nobj, frames, height + width) or not maps.is_contiguous():
+        raise RuntimeError(f"{what}: resample must be a contiguous int32 [nobj = {nobj}, F = {frames}, H + W = {height + width}] "
+                           f"table, got {tuple(maps.shape)}")
+
+
+def gather_planes(src, maps, out=None):
+    """zero-filled per-frame gather of contiguous fp16 planes [..., F, h, w] (leading dims = planes of ONE object):
+    out[.., f, y, x] = src[.., f, ymap_f[y], xmap_f[x]] or 0 where either index is outside.  ``maps``: device int32 [F, h + w]."""
+    _chk(src, "src"), _chk(maps, "maps", torch.int32)
+    if src.dim() < 3 or not src.is_contiguous():
+        raise RuntimeError(f"gather_planes: src must be contiguous [..., F, h, w], got {tuple(src.shape)}")
+    frames, h, w = src.shape[-3:]
+    if tuple(maps.shape) != (frames, h + w) or not maps.is_contiguous():
+        raise RuntimeError(f"gather_planes: maps must be a contiguous int32 [F = {frames}, h + w = {h + w}] table, got {tuple(maps.shape)}")
+    if out is None:
+        out = torch.empty_like(src)
+    _chk(out, "out")
+    if out.shape != src.shape or not out.is_contiguous():
+        raise RuntimeError("gather_planes: out must be contiguous and of src's shape")
+    check(lib.mvoc_gather_planes_f16(src.data_ptr(), out.data_ptr(), src.numel() // (frames * h * w), frames, h, w, maps.data_ptr(),
+                                     _stream()), "gather_planes")
     return out
 
 

@@ -18,6 +18,7 @@ import logging
 import os
 import weakref
 from copy import deepcopy
+from fractions import Fraction
 
 import torch
 
@@ -242,6 +243,100 @@ def resolve_variant_obj_offsets(variant_obj_offsets, nvar, n_obj, num_frames, fa
         return pls[0], None
     zero = tuple(((0, 0),) * num_frames for _ in range(n_obj))
     return None, tuple(zero if p is None else p for p in pls)
+
+
+MAX_SCALE_TERM = 64  # numerator and denominator of a reduced scale factor (obj_transforms)
+
+
+def _scale_fraction(v, what):
+    """one scale value of ``obj_transforms`` -> (p, q) reduced: an int, a "p/q" (or "p") string, or a float read by its
+    shortest decimal form (``Fraction(str(v))``: 1.5 -> 3/2, never the binary expansion)"""
+    try:
+        if isinstance(v, bool):
+            raise ValueError
+        if isinstance(v, int):
+            fr = Fraction(v)
+        elif isinstance(v, str):
+            num, _, den = v.partition("/")
+            fr = Fraction(int(num.strip()), int(den.strip()) if den else 1)
+        elif isinstance(v, float):
+            fr = Fraction(str(v))
+        else:
+            raise ValueError
+    except (ValueError, ZeroDivisionError):
+        raise ValueError(f"{what}: scale {v!r} is not an int, a 'p/q' string or a float") from None
+    p, q = fr.numerator, fr.denominator
+    if not (1 <= p <= MAX_SCALE_TERM and 1 <= q <= MAX_SCALE_TERM):
+        raise ValueError(f"{what}: scale {v!r} = {p}/{q} needs 1 <= p, q <= {MAX_SCALE_TERM} after reduction")
+    return p, q
+
+
+def normalize_obj_transforms(obj_transforms, n_obj, num_frames, lat_h, lat_w, factor=8):
+    """``obj_transforms`` of the sampling call -> (placement or None, transform or None).  One dict per object
+    with the optional keys ``offset`` (what an ``obj_offsets`` item accepts), ``scale`` (s or [sx, sy]; each an int, a "p/q"
+    string or a float), ``flip`` (None, "h", "v", "hv": "h" mirrors left-right) and ``anchor`` ([ax, ay], image pixels in
+    multiples of ``factor`` / 2; default the frame centre) -- the object is scaled and mirrored about the anchor, then moved.
+      (None, None)       no argument, or every object at identity: exactly a call without the argument
+      (placement, None)  every object at scale 1 without a flip: the placement ``normalize_obj_offsets`` returns
+      (None, transform)  else: per object (py, qy, px, qx, flip_y, flip_x, ay2, ax2, ((dy, dx) per frame)) on the
+                         ``lat_h`` x ``lat_w`` latent grid (ay2 / ax2 = twice the anchor), hashable
+    Anything else is a ValueError that names the object."""
+    if obj_transforms is None:
+        return None, None
+    if not isinstance(obj_transforms, (list, tuple)):
+        raise ValueError(f"obj_transforms: needs a list of {n_obj} dicts (one per object), got {obj_transforms!r}")
+    items = list(obj_transforms)
+    if len(items) != n_obj:
+        raise ValueError(f"obj_transforms: {len(items)} entries for {n_obj} objects (one per object)")
+    zero = ((0, 0),) * num_frames
+    out = []
+    for j, item in enumerate(items):
+        what = f"obj_transforms: object {j}"
+        item = {} if item is None else item
+        if not hasattr(item, "keys"):
+            raise ValueError(f"{what} needs a dict with any of offset, scale, flip, anchor, got {item!r}")
+        item = {k: item[k] for k in item.keys()}
+        unknown = sorted(set(item) - {"offset", "scale", "flip", "anchor"})
+        if unknown:
+            raise ValueError(f"{what} has the unknown key(s) {', '.join(map(repr, unknown))}; the keys are offset, scale, flip, anchor")
+        offs = zero
+        if item.get("offset") is not None:
+            try:
+                offs = normalize_obj_offsets([item["offset"]], 1, num_frames, factor)
+            except ValueError as e:
+                raise ValueError(f"{what}: offset: {str(e).replace('obj_offsets: object 0', '').strip(' ,:')}") from None
+            offs = zero if offs is None else offs[0]
+        scale = item.get("scale")
+        scale = 1 if scale is None else scale
+        if isinstance(scale, (list, tuple)):
+            if len(scale) != 2:
+                raise ValueError(f"{what}: scale {scale!r} needs one value or [sx, sy]")
+            sx, sy = scale
+        else:
+            sx = sy = scale
+        (px, qx), (py, qy) = _scale_fraction(sx, what), _scale_fraction(sy, what)
+        flip = item.get("flip")
+        if flip not in (None, "h", "v", "hv"):
+            raise ValueError(f"{what}: flip {flip!r} is not one of None, 'h', 'v', 'hv'")
+        flip_x, flip_y = flip in ("h", "hv"), flip in ("v", "hv")
+        anchor = item.get("anchor")
+        if anchor is None:
+            ax2, ay2 = int(lat_w), int(lat_h)
+        else:
+            anchor = list(anchor) if isinstance(anchor, (list, tuple)) else anchor
+            if not (isinstance(anchor, list) and len(anchor) == 2 and all(isinstance(v, int) and not isinstance(v, bool) for v in anchor)):
+                raise ValueError(f"{what}: anchor {anchor!r} needs [ax, ay] as integers (image pixels)")
+            if any((2 * v) % factor for v in anchor):
+                raise ValueError(f"{what}: anchor {tuple(anchor)} is not a multiple of {factor // 2} image pixels "
+                                 "(anchors sit on half latent pixels)")
+            ax2, ay2 = 2 * anchor[0] // factor, 2 * anchor[1] // factor
+        out.append((py, qy, px, qx, flip_y, flip_x, ay2, ax2, tuple(offs)))
+    plain = [t[0] == t[1] and t[2] == t[3] and not t[4] and not t[5] for t in out]
+    if all(plain):
+        if all(t[8] == zero for t in out):
+            return None, None
+        return tuple(t[8] for t in out), None
+    return None, tuple(out)
 
 
 def crosses_gemm_offset_line(nb, frames, h, w, width0):
@@ -651,6 +746,25 @@ class I2VGenXLPipeline:
             moved.append((s16.to(soft.dtype), h16.to(hard.dtype)))
         return moved, table
 
+    def transform_masks(self, masks, transform):
+        """the call's masks moved to destination coordinates under a transform: per object the soft and the hard
+        mask gathered through the object's per-frame index maps of the latent grid itself (``ops.level_axis_map`` with size ==
+        mask size), zero where the object is absent (``ops.gather_planes``) -> (masks in the form they came in, the device table
+        int32 [nobj, F, h + w] of those maps)"""
+        if len(transform) != len(masks):
+            raise ValueError(f"transform: {len(transform)} objects, {len(masks)} masks")
+        dev = self.device
+        frames, h, w = masks[0][0].shape[-3:]
+        if any(len(t[8]) != frames for t in transform):
+            raise ValueError(f"transform: every object needs {frames} per-frame offsets")
+        table = ops.resample_table(transform, h, w, h, w, dev)
+        moved = []
+        for j, (soft, hard) in enumerate(masks):
+            s16 = ops.gather_planes(soft.to(dev, H16).contiguous(), table[j])
+            h16 = ops.gather_planes(hard.to(dev, H16).contiguous(), table[j])
+            moved.append((s16.to(soft.dtype), h16.to(hard.dtype)))
+        return moved, table
+
     def place_variant_masks(self, masks, variant_placements):
         """the call's masks moved once per variant (``place_masks`` with each variant's placement) ->
         dict(place_dev = per variant the device table int32 [nobj, F, 2] of its latent-grid offsets,
@@ -663,7 +777,7 @@ class I2VGenXLPipeline:
                 "fusion_masks": [torch.stack([m[0].to(self.device, H16) for m in mk]).contiguous() for mk, _ in moved]}
 
     def make_composition_state(self, latents, cond, masks, guidance_scale, dedup_sources=None, variants=1, placement=None,
-                               variant_placements=None):
+                               variant_placements=None, transform=None):
         """static buffers + the captured iteration variants of the composition loop.
         cond: dict(encoder_hidden_states [n,77,D], image_embeddings [n,F,D], image_latents_first, image_latents, fps).
         The state keeps its OWN copy of ``cond``: the hoisted conditioning (``prepare_conditioning``) and the shared-CFG-prefix
@@ -677,8 +791,21 @@ class I2VGenXLPipeline:
         coordinates and are moved ONCE, here, to destination coordinates -- the state's masks everywhere (hooks, fusion).
         ``variant_placements`` (``resolve_variant_obj_offsets``; not with ``placement``): K placements, one per
         variant.  Each variant's masks are moved once, here; the engine takes them as (soft, hard) [K, nobj, F, h, w] stacks,
-        the fusion steps each variant's own.  The hooks keep ``masks`` as they came (shape checks and the mask key)."""
+        the fusion steps each variant's own.  The hooks keep ``masks`` as they came (shape checks and the mask key).
+        ``transform`` (``normalize_obj_transforms``; not with ``placement`` / ``variant_placements``): scale, mirror
+        and translation per object, one transform for all variants.  ``masks`` come in source coordinates and are gathered ONCE,
+        here, to destination coordinates (``transform_masks``); the fusion steps gather the objects' latents the same way."""
         cond = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in cond.items()}
+        resample_dev = None
+        if transform is not None:
+            if placement is not None or variant_placements is not None:
+                raise ValueError("transform is given together with placement / variant_placements: a transform carries its own "
+                                 "translation, and one transform serves all variants")
+            if self.unet.shard is not None:
+                raise RuntimeError("a transform does not combine with the frame shard: the section masks are cut to pixel slabs "
+                                   "and a gather crosses slabs")
+            transform = tuple(transform)
+            masks, resample_dev = self.transform_masks(masks, transform)
         vstate = None
         if variant_placements is not None:
             if placement is not None:
@@ -719,7 +846,8 @@ class I2VGenXLPipeline:
               "fusion_masks": torch.stack([m[0].to(dev, H16) for m in masks]).contiguous(),
               "fusion_objs": torch.empty((n_obj, 1) + tuple(latents.shape[1:]), dtype=H16, device=dev), "maps": {},
               "placement": placement, "place_dev": place_dev, "place_tables": [],
-              "variant_placements": variant_placements, "vplace": vstate})
+              "variant_placements": variant_placements, "vplace": vstate,
+              "transform": transform, "resample_dev": resample_dev})
         weak = weakref.ref(st)  # (the caller holds the state for as long as it steps it)
         st["build_map"] = lambda smap: self._composition_batch(weak(), smap, do_cfg)
         st["maps"][None] = st["build_map"](None)
@@ -771,6 +899,7 @@ class I2VGenXLPipeline:
             saved_pl, u.placement = u.placement, st["placement"]
             saved_vp, u.variant_placements = u.variant_placements, st["variant_placements"]
             saved_vm, u.variant_masks = u.variant_masks, None if st["vplace"] is None else st["vplace"]["masks"]
+            saved_tr, u.transform = u.transform, st["transform"]
             try:
                 noise = u.forward_ext(inp, st["t"], mcond["fps"], mcond["image_latents_first"], mcond["image_latents"],
                                       mcond["image_embeddings"], mcond["encoder_hidden_states"], multi_frame_guidance=False,
@@ -779,6 +908,7 @@ class I2VGenXLPipeline:
                 u.prune_source_tail, u.shared_prefix_chunks, u.source_chunks, u.variants = saved, saved_sp, saved_sc, saved_nv
                 u.placement = saved_pl
                 u.variant_placements, u.variant_masks = saved_vp, saved_vm
+                u.transform = saved_tr
                 u.prune_background = saved_pb
             # the engine's per-level offset tables are read by this state's captured graphs: they live as long as the state,
             # also after the engine drops its cache for another placement
@@ -786,6 +916,8 @@ class I2VGenXLPipeline:
                 st["place_tables"].append(u._place_cache[1])
             if st["variant_placements"] is not None and not any(d is u._vplace_cache[1] for d in st["place_tables"]):
                 st["place_tables"].append(u._vplace_cache[1])
+            if st["transform"] is not None and not any(d is u._resample_cache[1] for d in st["place_tables"]):
+                st["place_tables"].append(u._resample_cache[1])
             ops.ddim_step(x, noise[nb - nvar:nb].contiguous(), st["coef"],
                           v_uncond=noise[nb - 2 * nvar:nb - nvar].contiguous() if do_cfg else None, out=x)
 
@@ -810,6 +942,7 @@ class I2VGenXLPipeline:
                 bool(self.prune_source_tail), bool(st.get("share_cfg_prefix")), smap, st["nvar"]) + \
             (() if st["placement"] is None else (st["placement"],)) + \
             (() if st["variant_placements"] is None else ("variant_placements", st["variant_placements"])) + \
+            (() if st.get("transform") is None else ("transform", st["transform"])) + \
             (("no_background",) if self.background_dead(smap) else ())
 
     def composition_step(self, st, t, bg_latents, obj_latents, table_row, fuse=None):
@@ -828,7 +961,9 @@ class I2VGenXLPipeline:
                 lat = st["latents"][k:k + 1]
                 ops.latent_fusion(lat, bg_latents, st["fusion_objs"], vp["fusion_masks"][k], mix, rnf, out=lat)
             for j, o in enumerate(fobjs if vp is None else ()):
-                if st["place_dev"] is None:
+                if st.get("resample_dev") is not None:  # ... or is gathered with it (zero fill; the fusion masks are the gathered ones)
+                    ops.gather_planes(o.to(self.device, H16).contiguous(), st["resample_dev"][j], out=st["fusion_objs"][j])
+                elif st["place_dev"] is None:
                     st["fusion_objs"][j].copy_(o)
                 else:  # the object's inverted latents move with it (zero fill; the fusion masks are the shifted ones)
                     ops.shift_planes(o.to(self.device, H16).contiguous(), st["place_dev"][j], out=st["fusion_objs"][j])
@@ -868,7 +1003,7 @@ class I2VGenXLPipeline:
             fusion_steps=(0, 3), ddim_init_latents_t_idx=1, ddim_inv_prompt=None, obj_mask=None, obj_width_height=None,
             obj_ddim_latents_idx_offset=None, obj_random_noise_fusion=False, random_noise_ratio=0.0,
             bg_inv_latents_path=None, obj_ddim_latents_path=None, obj_masks_tensors=None, obj_offsets=None,
-            variant_obj_offsets=None):
+            variant_obj_offsets=None, obj_transforms=None):
         """PnP composition sampling.  ``obj_mask``: list of mask paths (preprocessed by ``mvoc_amd.utils.mask_preprocess``)
         or pass ``obj_masks_tensors`` = list of (float [1,4,F,h,w], bool [1,4,F,h,w]) directly.
 
@@ -884,7 +1019,14 @@ class I2VGenXLPipeline:
 
         ``variant_obj_offsets`` (not together with ``obj_offsets``): a list of K items, one per variant, each None
         or a value ``obj_offsets`` accepts -- variant k composes the objects at ITS offsets over the one set of source chunks.
-        All items None / zero: exactly a call without it; all items equal: exactly the ``obj_offsets`` call."""
+        All items None / zero: exactly a call without it; all items equal: exactly the ``obj_offsets`` call.
+
+        ``obj_transforms`` (not together with ``obj_offsets`` / ``variant_obj_offsets``): one dict per object with
+        the optional keys ``offset`` (an ``obj_offsets`` item), ``scale`` (s or [sx, sy]: int, "p/q" or float; p, q <= 64),
+        ``flip`` (None, "h", "v", "hv") and ``anchor`` ([ax, ay], image pixels in multiples of 4; default the frame centre) --
+        the object is scaled and mirrored about the anchor (nearest neighbour, exact) and then moved, without re-inverting
+        anything (``normalize_obj_transforms``; shared by the variants, not with a frame shard).  Every object at identity:
+        exactly a call without it; translation only: exactly the ``obj_offsets`` call.  ``obj_width_height`` stays ignored."""
         from .utils import mask_preprocess
         # ---- the variants of this call (one with scalar arguments: the batch, kernels and launches of a single composition)
         m_rep = int(num_videos_per_prompt)
@@ -929,11 +1071,21 @@ class I2VGenXLPipeline:
         if obj_offsets is not None and variant_obj_offsets is not None:
             raise ValueError("obj_offsets and variant_obj_offsets are both given: a call places its objects once for all "
                              "variants or per variant")
+        if obj_transforms is not None and (obj_offsets is not None or variant_obj_offsets is not None):
+            raise ValueError("obj_transforms is given together with obj_offsets / variant_obj_offsets: a transform carries its "
+                             "own offset, and one transform serves all variants")
         placement = normalize_obj_offsets(obj_offsets, n_obj, num_frames, self.vae_scale_factor)
         variant_placements = None
         if variant_obj_offsets is not None:
             placement, variant_placements = resolve_variant_obj_offsets(variant_obj_offsets, nvar, n_obj, num_frames,
                                                                         self.vae_scale_factor)
+        transform = None
+        if obj_transforms is not None:
+            placement, transform = normalize_obj_transforms(obj_transforms, n_obj, num_frames, height // self.vae_scale_factor,
+                                                            width // self.vae_scale_factor, self.vae_scale_factor)
+        if transform is not None and self.unet.shard is not None:
+            raise RuntimeError("obj_transforms do not combine with the frame shard: the section masks are cut to pixel slabs and a "
+                               "gather crosses slabs")
         if variant_placements is not None and self.unet.shard is not None:
             raise RuntimeError("variant_obj_offsets do not combine with the frame shard: the section masks are cut to pixel "
                                "slabs and a shift crosses slabs")
@@ -1023,7 +1175,8 @@ class I2VGenXLPipeline:
         self.unet.check_variant_schedules(nvar)  # per-variant injection schedules are hook state (pnp_utils): one entry per variant
         st = self.make_composition_state(latents, cond, obj_masks_tensors, scales if nvar > 1 else guidance_scale, variants=nvar,
                                          **({} if placement is None else {"placement": placement}),
-                                         **({} if variant_placements is None else {"variant_placements": variant_placements}))
+                                         **({} if variant_placements is None else {"variant_placements": variant_placements}),
+                                         **({} if transform is None else {"transform": transform}))
         table, index = sched.coef_table(self.device, guidance_scale)
         if nvar > 1:  # [steps, K, 5]: a step's coefficient rows are one view, whatever K is
             table = torch.stack([sched.coef_table(self.device, g)[0] for g in scales], 1).contiguous()

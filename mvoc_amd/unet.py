@@ -697,6 +697,15 @@ class I2VGenXLUNet:
         self.variant_placements = None
         self.variant_masks = None
         self._vplace_cache = (None, {})
+        # Scale and mirror (pipeline.py obj_transforms): None, or a hashable tuple -- per object (py, qy, px, qx,
+        # flip_y, flip_x, ay2, ax2, ((dy, dx) per frame)): scale p / q per axis, mirror flags, twice the anchor and the per-frame
+        # translation, all on the latent grid.  Every injection site then reads object j of frame f at the pixel its per-axis maps
+        # name (ops.level_axis_map for the site's H x W) through the _resampled blend entries; the hook masks are in destination
+        # coordinates already (the pipeline gathers them once per call).  None = today's calls.  Set and restored around its forward
+        # by the composition loop, like placement; shared by the variants.  Not with placement / variant_placements, not with a
+        # frame shard.
+        self.transform = None
+        self._resample_cache = (None, {})
 
     def set_frame_shard(self, shard):
         """Frame-shard every forward over the ranks of ``shard`` (``mvoc_amd.frame_shard``): each rank receives the FULL
@@ -949,13 +958,40 @@ class I2VGenXLUNet:
                                f"{', '.join(str(n) for n in masks.shape)}] (the hook masks per variant)")
         return stack
 
+    def resample_table(self, mask_list, H, W):
+        """the ``resample=`` argument of a site's blend at H x W under ``transform``: the device table [nobj, F, H + W] of per-axis
+        index maps, cached per (transform, H, W, mh, mw) and dropped when the transform changes"""
+        tr = self.transform
+        if self.placement is not None or self.variant_placements is not None:
+            raise RuntimeError("transform is set together with placement / variant_placements: a transform carries its own "
+                               "translation, and one transform serves all variants")
+        if self.shard is not None:
+            raise RuntimeError("a transform does not combine with the frame shard: the section masks are cut to pixel slabs "
+                               "and a gather crosses slabs")
+        if len(tr) != len(mask_list):
+            raise RuntimeError(f"transform holds {len(tr)} objects, the hooks carry {len(mask_list)} masks")
+        if self._resample_cache[0] != tr:
+            self._resample_cache = (tr, {})
+        mh, mw = self._all_frame_masks(mask_list)[0].shape[2:]
+        key = (H, W, mh, mw)
+        tab = self._resample_cache[1].get(key)
+        if tab is None:
+            tab = self._resample_cache[1][key] = ops.resample_table(tr, H, W, mh, mw, self.device)
+        return tab
+
     def place_kw(self, mask_list, H, W):
-        """keyword arguments of a site's blend call: none without a placement (exactly today's call), else ``place=``"""
+        """keyword arguments of a site's blend call: none without a placement or transform (exactly today's call), else
+        ``place=`` -- or, under ``transform``, ``resample=`` the level's table"""
+        if self.transform is not None:
+            return {"resample": self.resample_table(mask_list, H, W)}
         tab = self.place_table(mask_list, H, W)
         return {} if tab is None else {"place": tab}
 
     def pnp_batch(self, B, mask_list):
         """(ndst, source map) of an injection site's batch of B chunks (``check_pnp_batch`` under ``source_chunks``)"""
+        if self.transform is not None and self.shard is not None:
+            raise RuntimeError("a transform does not combine with the frame shard: the section masks are cut to pixel slabs "
+                               "and a gather crosses slabs")
         if self.placement is not None and self.shard is not None:
             raise RuntimeError("a placement does not combine with the frame shard: the section masks are cut to pixel slabs "
                                "and a shift crosses slabs")
@@ -977,7 +1013,8 @@ class I2VGenXLUNet:
             nsrc = (len(mask_list) if smap is None else smap[0] - 1)
             chunks = tuple(range(nsrc)) if smap is None else tuple(c - 1 for c in smap[1])
             ndst = self.check_pnp_batch(B, mask_list, nsrc, self.variants, no_background=True)
-            positional = smap is None and self.variants == 1 and self.placement is None and self.variant_placements is None
+            positional = smap is None and self.variants == 1 and self.placement is None and self.variant_placements is None \
+                and self.transform is None
             return ndst, (None if positional else (nsrc, chunks))
         return self.check_pnp_batch(B, mask_list, None if smap is None else smap[0], self.variants), smap
 

@@ -20,6 +20,9 @@ also runs the K compositions one by one in the same process and reports the rati
 --place "dx,dy;dx,dy" (opt-in): the entry's `obj_offset` (DESIGN.md 6k) -- one pair per object, image pixels in multiples of 8;
 the composition then places the objects that far from where they sit in their clips.  Reported like --variants (K = 1 unless
 --variants is given too).
+--transform "scale=3/2,flip=h,offset=64,0;scale=1/2" (opt-in): the entry's `obj_transform` -- one item per object:
+scale (s or sx,sy; ints or p/q), flip (h, v, hv), offset (dx,dy) and anchor (ax,ay); nearest-neighbour scale and mirror about the
+anchor, then the offset.  Reported like --place.
 --variant-place "dx,dy;dx,dy|dx,dy;dx,dy|.." (opt-in, needs --variants K): K placements separated by `|`, each in the format of
 --place -- the variants' `placement` key: every variant composes the objects at its own offsets over the one set
 of source chunks.  With --sequential the K single jobs each take their variant's placement as `obj_offset`.
@@ -370,6 +373,38 @@ def parse_place(text):
     return out
 
 
+def parse_transform(text):
+    """"scale=3/2,flip=h,offset=64,0;scale=1/2" -> one dict per object (`;` separates the objects): the entry's `obj_transform`.
+    scale = s or sx,sy (ints or p/q); flip = h, v or hv; offset = dx,dy; anchor = ax,ay; an empty item is the identity"""
+    out = []
+    for j, item in enumerate(text.split(";")):
+        fields = []
+        for tok in (t.strip() for t in item.split(",") if t.strip()):
+            if "=" in tok:
+                k, _, v = tok.partition("=")
+                fields.append([k.strip(), [v.strip()]])
+            elif fields:
+                fields[-1][1].append(tok)
+            else:
+                raise SystemExit(f"--transform, object {j}: {tok!r} has no key (scale=, flip=, offset=, anchor=)")
+        d = {}
+        for k, vals in fields:
+            try:
+                if k == "scale" and len(vals) in (1, 2):
+                    sc = [int(v) if v.lstrip("-").isdigit() else v for v in vals]
+                    d[k] = sc[0] if len(sc) == 1 else sc
+                elif k == "flip" and len(vals) == 1:
+                    d[k] = vals[0]
+                elif k in ("offset", "anchor") and len(vals) == 2:
+                    d[k] = [int(v) for v in vals]
+                else:
+                    raise ValueError
+            except ValueError:
+                raise SystemExit(f"--transform, object {j}: cannot read {k}={','.join(vals)}")
+        out.append(d)
+    return out
+
+
 def parse_variant_place(text, variants):
     """"dx,dy;dx,dy|dx,dy;dx,dy" -> K placements, each as ``parse_place`` returns it (`|` separates the variants)"""
     if not variants:
@@ -389,7 +424,7 @@ def parse_variant_place(text, variants):
 
 
 def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, thresholds=None, sequential=False, place=None,
-                 variant_place=None):
+                 variant_place=None, transform=None):
     """K prompts and seeds over the boat_surf-shaped job (three distinct sources), one composition loop (composite.py `variants`).
     ``thresholds``: K values of pnp_spatial_attn_t, one per variant (the variants' `pnp` key); ``sequential``: after
     the one loop, the same K compositions one by one (single entries with the flat threshold) for the comparison."""
@@ -429,6 +464,8 @@ def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, threshol
     centry = dict(boat_surf_entry(size), variants=var)
     if place is not None:  # shared by the variants: an entry key
         centry["obj_offset"] = [list(p) for p in place]
+    if transform is not None:  # scale / mirror / offset per object: an entry key, shared by the variants
+        centry["obj_transform"] = [dict(t) for t in transform]
     with StageTimer(pl) as timer:
         composite.main(ct, [centry], dev, synthetic=True)
     res = timer.result()
@@ -443,6 +480,8 @@ def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, threshol
         res["obj_offset"] = [list(p) for p in place]
     if variant_place is not None:
         res["variant_placement"] = [[list(q) for q in p] for p in variant_place]
+    if transform is not None:
+        res["obj_transform"] = [dict(t) for t in transform]
     if thresholds is not None:
         res["variant_thresholds"] = [float(t) for t in thresholds]
         res["output_suffix_of"] = {d: where[d] for d in dirs}
@@ -455,6 +494,8 @@ def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, threshol
                 e["obj_offset"] = [list(p) for p in place]
             if variant_place is not None:  # the single job of variant k: its placement as the entry's
                 e["obj_offset"] = [list(q) for q in variant_place[k]]
+            if transform is not None:
+                e["obj_transform"] = [dict(t) for t in transform]
             if thresholds is not None:
                 e["pnp_spatial_attn_t"] = float(thresholds[k])
             with StageTimer(pl) as t1:
@@ -494,13 +535,16 @@ if __name__ == "__main__":
                     help="place the objects at composition time: one dx,dy per object, image pixels in multiples of 8 (`obj_offset`)")
     ap.add_argument("--variant-place", type=str, default=None, metavar="dx,dy;dx,dy|..",
                     help="with --variants K: K placements separated by |, each in the format of --place (the variants' `placement` key)")
+    ap.add_argument("--transform", type=str, default=None, metavar="scale=p/q,flip=h,offset=dx,dy;..",
+                    help="scale / mirror / place the objects at composition time: one item per object separated by ; (`obj_transform`)")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
-    if a.variants or a.place or a.variant_place:
+    if a.variants or a.place or a.variant_place or a.transform:
         th = None if a.variant_thresholds is None else [float(x) for x in a.variant_thresholds.split(",")]
         place = None if a.place is None else parse_place(a.place)
         vplace = None if a.variant_place is None else parse_variant_place(a.variant_place, a.variants)
-        print(json.dumps(run_variants(a.frames, a.size, a.steps, a.keep, a.variants or 1, th, a.sequential, place, vplace)),
+        transform = None if a.transform is None else parse_transform(a.transform)
+        print(json.dumps(run_variants(a.frames, a.size, a.steps, a.keep, a.variants or 1, th, a.sequential, place, vplace, transform)),
               flush=True)
     else:
         fn = run_shared_source if a.shared_source else run
