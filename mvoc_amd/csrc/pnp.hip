@@ -6,6 +6,8 @@
 // Traffic per injection site (spatial Q/K at the 320-channel level, B=5, F=16, 64x64): read base + 2 objects,
 // write 2 destination chunks, for Q and K = 10 x 41.9 MB + masks (1 fp16 per (frame, pixel), never expanded to
 // [F,H,W,C]) = 419.6 MB -- the reference moves several times that through rearrange/repeat copies.
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -131,61 +133,28 @@ __global__ __launch_bounds__(256) void pnp_nchw_kernel(const PnpArgs p) {
   }
 }
 
-// ---- K variants over one set of source chunks ------------------------------------------------
-// Batch [s_0..s_{nsrc-1}, u_1..u_K, c_1..c_K] (ndst == 1: [s.., c_1..c_K]).  The object vectors and mask values of a work item
-// are read ONCE and stay in registers across the variant loop: NOBJ is a template parameter, so ov[] / m[] are indexed by
-// unrolled constants only (a run-time-indexed array would go to scratch, see PnpArgs.obj_map).  Per variant the arithmetic
-// is that of the kernels above: blend16 in object order on the variant's base.
+// ---- the blend-scatter family: K variants over one set of source chunks -------------------------------
+// Batch [s_0..s_{nsrc-1}, u_1..u_K, c_1..c_K] (ndst == 1: [s.., c_1..c_K]).  Ten kernels, every one composed from the same
+// four pieces:
+//   item geometry   Tokens / Nchw<VEC>::init: the work item's frame, pixel(s) and offsets
+//   object load     ::load<S>: NOBJ object vectors and their mask values, by the source rule S --
+//                     DIRECT  the object at the destination pixel (vector load; the mask as float)
+//                     SHIFT   at (py - dfy, px - dfx) of an offset table (placed_src)
+//                     MAP     at (ymap[py], xmap[px]) of per-axis index maps (resampled_src)
+//                   SHIFT / MAP: where the source pixel lies outside the frame the object is absent, value 0 and mask 0 enter
+//                   the arithmetic like any other pair (it is not skipped: a -0.0 base becomes +0.0 as under a zero mask); the
+//                   masks are in destination coordinates and sampled at the destination pixel
+//   blend           one base vector over the NOBJ objects in object order: blend16 (DIRECT) or blend16_h (SHIFT / MAP)
+//   variant scatter blend_scatter: objects loaded ONCE and kept in registers across the variant loop; one blend for every
+//                   variant when the base is chunk 0, else per variant on its own cond chunk; ndst stores per variant; SEL =
+//                   bit k of `active` clear: variant k's chunks are neither read nor written (wave-uniform, a kernel argument)
+// blend_scatter_per_variant is the same pieces with the object load INSIDE the variant loop.
+//   _variants = <DIRECT, no SEL>   _variants_sel = <DIRECT, SEL>   _placed = <SHIFT, SEL>   _resampled = <MAP, SEL>
+//   _placed_variants = per-variant <SHIFT, SEL>
+// NOBJ is a template parameter, so the object arrays are indexed by unrolled constants only (a run-time-indexed array would go
+// to scratch, see PnpArgs.obj_map).
 __device__ __forceinline__ int var_dst(const PnpArgs& p, int nvar, int d, int k) {  // d: 0 = first block of destinations
   return p.nsrc + d * nvar + k;
-}
-
-template <int NOBJ>
-__global__ __launch_bounds__(256) void pnp_tokens_variants_kernel(const PnpArgs p, const int nvar) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= p.total) return;
-  half_t* x = p.x[blockIdx.y];
-  const int c8n = p.channels >> 3;
-  const int c8 = (int)(idx % c8n);
-  const long fp = idx / c8n;
-  const int hw = p.height * p.width;
-  const int f = (int)(fp / hw), px = (int)(fp % hw);
-  const int py = px / p.width, pxx = px - py * p.width;
-  const int my = nearest_src(py, p.sy, p.mask_h), mx = nearest_src(pxx, p.sx, p.mask_w);
-  const long off = (long)f * p.f_stride + (long)px * p.p_stride + c8 * 8;
-  half8_t ov[NOBJ];
-  float m[NOBJ];
-#pragma unroll
-  for (int j = 0; j < NOBJ; ++j) {
-    m[j] = (float)p.masks[(((long)j * p.frames + f) * p.mask_h + my) * p.mask_w + mx];
-    ov[j] = *reinterpret_cast<const half8_t*>(x + obj_chunk<true>(p, j) * p.chunk_stride + off);
-  }
-  half8_t o;
-  if (p.base_chunk0) {  // one blend for every variant
-    const half8_t bv = *reinterpret_cast<const half8_t*>(x + off);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float inj = (float)bv[e];
-#pragma unroll
-      for (int j = 0; j < NOBJ; ++j) inj = blend16(inj, (float)ov[j][e], m[j]);
-      o[e] = (half_t)inj;
-    }
-  }
-  for (int k = 0; k < nvar; ++k) {
-    half_t* cond = x + var_dst(p, nvar, p.ndst - 1, k) * p.chunk_stride + off;
-    if (!p.base_chunk0) {
-      const half8_t bv = *reinterpret_cast<const half8_t*>(cond);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float inj = (float)bv[e];
-#pragma unroll
-        for (int j = 0; j < NOBJ; ++j) inj = blend16(inj, (float)ov[j][e], m[j]);
-        o[e] = (half_t)inj;
-      }
-    }
-    if (p.ndst == 2) *reinterpret_cast<half8_t*>(x + var_dst(p, nvar, 0, k) * p.chunk_stride + off) = o;
-    *reinterpret_cast<half8_t*>(cond) = o;
-  }
 }
 
 template <int VEC>
@@ -200,177 +169,10 @@ __device__ __forceinline__ void st_vec(half_t* dst, const half_t (&t)[VEC]) {
   else dst[0] = t[0];
 }
 
-template <int VEC, int NOBJ>
-__global__ __launch_bounds__(256) void pnp_nchw_variants_kernel(const PnpArgs p, const int nvar) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= p.total) return;
-  half_t* x = p.x[blockIdx.y];
-  const int hw = p.height * p.width;
-  const int pvn = hw / VEC;
-  const int pv = (int)(idx % pvn);
-  const long fc = idx / pvn;
-  const int f = (int)(fc / p.channels);
-  const long off = fc * hw + (long)pv * VEC;  // (f*C + c)*HW + p
-  const long chunk = (long)p.frames * p.channels * hw;
-  half_t ov[NOBJ][VEC];
-  float m[NOBJ][VEC];
-#pragma unroll
-  for (int j = 0; j < NOBJ; ++j) {
-    ld_vec<VEC>(ov[j], x + obj_chunk<true>(p, j) * chunk + off);
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-      const int px = pv * VEC + e;
-      const int py = px / p.width, pxx = px - py * p.width;
-      const int my = nearest_src(py, p.sy, p.mask_h), mx = nearest_src(pxx, p.sx, p.mask_w);
-      m[j][e] = (float)p.masks[(((long)j * p.frames + f) * p.mask_h + my) * p.mask_w + mx];
-    }
-  }
-  half_t tmp[VEC];
-  if (p.base_chunk0) {
-    ld_vec<VEC>(tmp, x + off);
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-      float inj = (float)tmp[e];
-#pragma unroll
-      for (int j = 0; j < NOBJ; ++j) inj = blend16(inj, (float)ov[j][e], m[j][e]);
-      tmp[e] = (half_t)inj;
-    }
-  }
-  for (int k = 0; k < nvar; ++k) {
-    half_t* cond = x + var_dst(p, nvar, p.ndst - 1, k) * chunk + off;
-    if (!p.base_chunk0) {
-      ld_vec<VEC>(tmp, cond);
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) {
-        float inj = (float)tmp[e];
-#pragma unroll
-        for (int j = 0; j < NOBJ; ++j) inj = blend16(inj, (float)ov[j][e], m[j][e]);
-        tmp[e] = (half_t)inj;
-      }
-    }
-    if (p.ndst == 2) st_vec<VEC>(x + var_dst(p, nvar, 0, k) * chunk + off, tmp);
-    st_vec<VEC>(cond, tmp);
-  }
-}
-
-// ---- per-variant injection schedules -----------------------------------------------------------
-// The variants kernels with a by-value bitmask: bit k of `active` set = variant k injects at this launch.  The chunks of a
-// variant whose bit is clear are neither read nor written; the skip is wave-uniform (a kernel argument).  Kernels of their
-// own, so the instantiations above compile as they always did.
-template <int NOBJ>
-__global__ __launch_bounds__(256) void pnp_tokens_variants_sel_kernel(const PnpArgs p, const int nvar, const unsigned active) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= p.total) return;
-  half_t* x = p.x[blockIdx.y];
-  const int c8n = p.channels >> 3;
-  const int c8 = (int)(idx % c8n);
-  const long fp = idx / c8n;
-  const int hw = p.height * p.width;
-  const int f = (int)(fp / hw), px = (int)(fp % hw);
-  const int py = px / p.width, pxx = px - py * p.width;
-  const int my = nearest_src(py, p.sy, p.mask_h), mx = nearest_src(pxx, p.sx, p.mask_w);
-  const long off = (long)f * p.f_stride + (long)px * p.p_stride + c8 * 8;
-  half8_t ov[NOBJ];
-  float m[NOBJ];
-#pragma unroll
-  for (int j = 0; j < NOBJ; ++j) {
-    m[j] = (float)p.masks[(((long)j * p.frames + f) * p.mask_h + my) * p.mask_w + mx];
-    ov[j] = *reinterpret_cast<const half8_t*>(x + obj_chunk<true>(p, j) * p.chunk_stride + off);
-  }
-  half8_t o;
-  if (p.base_chunk0) {  // one blend for every injecting variant
-    const half8_t bv = *reinterpret_cast<const half8_t*>(x + off);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float inj = (float)bv[e];
-#pragma unroll
-      for (int j = 0; j < NOBJ; ++j) inj = blend16(inj, (float)ov[j][e], m[j]);
-      o[e] = (half_t)inj;
-    }
-  }
-  for (int k = 0; k < nvar; ++k) {
-    if (!((active >> k) & 1u)) continue;
-    half_t* cond = x + var_dst(p, nvar, p.ndst - 1, k) * p.chunk_stride + off;
-    if (!p.base_chunk0) {
-      const half8_t bv = *reinterpret_cast<const half8_t*>(cond);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float inj = (float)bv[e];
-#pragma unroll
-        for (int j = 0; j < NOBJ; ++j) inj = blend16(inj, (float)ov[j][e], m[j]);
-        o[e] = (half_t)inj;
-      }
-    }
-    if (p.ndst == 2) *reinterpret_cast<half8_t*>(x + var_dst(p, nvar, 0, k) * p.chunk_stride + off) = o;
-    *reinterpret_cast<half8_t*>(cond) = o;
-  }
-}
-
-template <int VEC, int NOBJ>
-__global__ __launch_bounds__(256) void pnp_nchw_variants_sel_kernel(const PnpArgs p, const int nvar, const unsigned active) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= p.total) return;
-  half_t* x = p.x[blockIdx.y];
-  const int hw = p.height * p.width;
-  const int pvn = hw / VEC;
-  const int pv = (int)(idx % pvn);
-  const long fc = idx / pvn;
-  const int f = (int)(fc / p.channels);
-  const long off = fc * hw + (long)pv * VEC;  // (f*C + c)*HW + p
-  const long chunk = (long)p.frames * p.channels * hw;
-  half_t ov[NOBJ][VEC];
-  float m[NOBJ][VEC];
-#pragma unroll
-  for (int j = 0; j < NOBJ; ++j) {
-    ld_vec<VEC>(ov[j], x + obj_chunk<true>(p, j) * chunk + off);
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-      const int px = pv * VEC + e;
-      const int py = px / p.width, pxx = px - py * p.width;
-      const int my = nearest_src(py, p.sy, p.mask_h), mx = nearest_src(pxx, p.sx, p.mask_w);
-      m[j][e] = (float)p.masks[(((long)j * p.frames + f) * p.mask_h + my) * p.mask_w + mx];
-    }
-  }
-  half_t tmp[VEC];
-  if (p.base_chunk0) {
-    ld_vec<VEC>(tmp, x + off);
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-      float inj = (float)tmp[e];
-#pragma unroll
-      for (int j = 0; j < NOBJ; ++j) inj = blend16(inj, (float)ov[j][e], m[j][e]);
-      tmp[e] = (half_t)inj;
-    }
-  }
-  for (int k = 0; k < nvar; ++k) {
-    if (!((active >> k) & 1u)) continue;
-    half_t* cond = x + var_dst(p, nvar, p.ndst - 1, k) * chunk + off;
-    if (!p.base_chunk0) {
-      ld_vec<VEC>(tmp, cond);
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) {
-        float inj = (float)tmp[e];
-#pragma unroll
-        for (int j = 0; j < NOBJ; ++j) inj = blend16(inj, (float)ov[j][e], m[j][e]);
-        tmp[e] = (half_t)inj;
-      }
-    }
-    if (p.ndst == 2) st_vec<VEC>(x + var_dst(p, nvar, 0, k) * chunk + off, tmp);
-    st_vec<VEC>(cond, tmp);
-  }
-}
-
-// ---- placement: per-frame integer translation of the objects ----------------------------------------
-// The _variants_sel kernels with one addition: object j of frame f is read at the pixel (py - dfy, px - dfx), (dfy, dfx) =
-// place[(j * frames + f) * 2 ..] -- a device table of int32 pairs for THIS site's H x W, constant for the whole call.  Where
-// that pixel lies outside the frame the object is absent: value 0 and mask 0 enter blend16 like any other pair (the arithmetic
-// is not skipped, a -0.0 base becomes +0.0 as under a zero mask).  The masks are already in destination coordinates and are
-// sampled at the destination pixel.  Kernels of their own, so the instantiations above compile as they always did.
-//
 // blend16 on fp16 operands, one correctly rounded fp16 operation per statement (the same values as blend16: each of its float
-// operations on fp16 inputs is rounded to fp16 at once).  The placed kernels SELECT their object value and mask (absent: 0, 0), and
+// operations on fp16 inputs is rounded to fp16 at once).  The SHIFT / MAP loads SELECT their object value and mask (absent: 0, 0), and
 // with float operands behind a select hipcc forms r16(obj * m) as a mixed-precision fma with a +0.0 addend, which turns a -0.0
-// product into +0.0 -- the kernels above multiply in fp16 and keep it.  Written in fp16, no such choice is left to the compiler.
+// product into +0.0 -- the DIRECT kernels multiply in fp16 and keep it.  Written in fp16, no such choice is left to the compiler.
 __device__ __forceinline__ half_t blend16_h(half_t inj, half_t obj, half_t m) {
   const half_t om = (half_t)1.0f - m;
   const half_t a = inj * om;
@@ -378,6 +180,8 @@ __device__ __forceinline__ half_t blend16_h(half_t inj, half_t obj, half_t m) {
   return a + b;
 }
 
+// SHIFT: place = int32 [nobj][frames][2], (dfy, dfx) of object j in frame f -- a device table for THIS site's H x W, constant
+// for the whole call
 __device__ __forceinline__ bool placed_src(const int* __restrict__ place, int j, int frames, int f, int py, int px, int h, int w,
                                            long& spix) {
   const int* o = place + ((long)j * frames + f) * 2;
@@ -386,257 +190,9 @@ __device__ __forceinline__ bool placed_src(const int* __restrict__ place, int j,
   return sy >= 0 && sy < h && sx >= 0 && sx < w;
 }
 
-template <int NOBJ>
-__global__ __launch_bounds__(256) void pnp_tokens_placed_kernel(const PnpArgs p, const int nvar, const unsigned active,
-                                                                const int* __restrict__ place) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= p.total) return;
-  half_t* x = p.x[blockIdx.y];
-  const int c8n = p.channels >> 3;
-  const int c8 = (int)(idx % c8n);
-  const long fp = idx / c8n;
-  const int hw = p.height * p.width;
-  const int f = (int)(fp / hw), px = (int)(fp % hw);
-  const int py = px / p.width, pxx = px - py * p.width;
-  const int my = nearest_src(py, p.sy, p.mask_h), mx = nearest_src(pxx, p.sx, p.mask_w);
-  const long foff = (long)f * p.f_stride + c8 * 8;
-  const long off = foff + (long)px * p.p_stride;
-  half8_t ov[NOBJ];
-  half_t m[NOBJ];
-#pragma unroll
-  for (int j = 0; j < NOBJ; ++j) {
-    long spix;
-    const bool in = placed_src(place, j, p.frames, f, py, pxx, p.height, p.width, spix);
-    m[j] = (half_t)0.0f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) ov[j][e] = (half_t)0.0f;
-    if (in) {
-      m[j] = p.masks[(((long)j * p.frames + f) * p.mask_h + my) * p.mask_w + mx];
-      ov[j] = *reinterpret_cast<const half8_t*>(x + obj_chunk<true>(p, j) * p.chunk_stride + foff + spix * p.p_stride);
-    }
-  }
-  half8_t o;
-  if (p.base_chunk0) {  // one blend for every injecting variant
-    const half8_t bv = *reinterpret_cast<const half8_t*>(x + off);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      half_t inj = bv[e];
-#pragma unroll
-      for (int j = 0; j < NOBJ; ++j) inj = blend16_h(inj, ov[j][e], m[j]);
-      o[e] = inj;
-    }
-  }
-  for (int k = 0; k < nvar; ++k) {
-    if (!((active >> k) & 1u)) continue;
-    half_t* cond = x + var_dst(p, nvar, p.ndst - 1, k) * p.chunk_stride + off;
-    if (!p.base_chunk0) {
-      const half8_t bv = *reinterpret_cast<const half8_t*>(cond);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        half_t inj = bv[e];
-#pragma unroll
-        for (int j = 0; j < NOBJ; ++j) inj = blend16_h(inj, ov[j][e], m[j]);
-        o[e] = inj;
-      }
-    }
-    if (p.ndst == 2) *reinterpret_cast<half8_t*>(x + var_dst(p, nvar, 0, k) * p.chunk_stride + off) = o;
-    *reinterpret_cast<half8_t*>(cond) = o;
-  }
-}
-
-// NCHW: a shift in x breaks the 8-pixel alignment of the object rows, so the object values are read one pixel at a time (each
-// of the VEC pixels of a work item has its own source pixel); the base and the destinations keep the vector accesses
-template <int VEC, int NOBJ>
-__global__ __launch_bounds__(256) void pnp_nchw_placed_kernel(const PnpArgs p, const int nvar, const unsigned active,
-                                                              const int* __restrict__ place) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= p.total) return;
-  half_t* x = p.x[blockIdx.y];
-  const int hw = p.height * p.width;
-  const int pvn = hw / VEC;
-  const int pv = (int)(idx % pvn);
-  const long fc = idx / pvn;
-  const int f = (int)(fc / p.channels);
-  const long off = fc * hw + (long)pv * VEC;  // (f*C + c)*HW + p
-  const long chunk = (long)p.frames * p.channels * hw;
-  half_t ov[NOBJ][VEC];
-  half_t m[NOBJ][VEC];
-#pragma unroll
-  for (int j = 0; j < NOBJ; ++j) {
-    const half_t* src = x + obj_chunk<true>(p, j) * chunk + fc * hw;
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-      const int px = pv * VEC + e;
-      const int py = px / p.width, pxx = px - py * p.width;
-      long spix;
-      const bool in = placed_src(place, j, p.frames, f, py, pxx, p.height, p.width, spix);
-      m[j][e] = (half_t)0.0f;
-      ov[j][e] = (half_t)0.0f;
-      if (in) {
-        const int my = nearest_src(py, p.sy, p.mask_h), mx = nearest_src(pxx, p.sx, p.mask_w);
-        m[j][e] = p.masks[(((long)j * p.frames + f) * p.mask_h + my) * p.mask_w + mx];
-        ov[j][e] = src[spix];
-      }
-    }
-  }
-  half_t tmp[VEC];
-  if (p.base_chunk0) {
-    ld_vec<VEC>(tmp, x + off);
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-      half_t inj = tmp[e];
-#pragma unroll
-      for (int j = 0; j < NOBJ; ++j) inj = blend16_h(inj, ov[j][e], m[j][e]);
-      tmp[e] = inj;
-    }
-  }
-  for (int k = 0; k < nvar; ++k) {
-    if (!((active >> k) & 1u)) continue;
-    half_t* cond = x + var_dst(p, nvar, p.ndst - 1, k) * chunk + off;
-    if (!p.base_chunk0) {
-      ld_vec<VEC>(tmp, cond);
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) {
-        half_t inj = tmp[e];
-#pragma unroll
-        for (int j = 0; j < NOBJ; ++j) inj = blend16_h(inj, ov[j][e], m[j][e]);
-        tmp[e] = inj;
-      }
-    }
-    if (p.ndst == 2) st_vec<VEC>(x + var_dst(p, nvar, 0, k) * chunk + off, tmp);
-    st_vec<VEC>(cond, tmp);
-  }
-}
-
-// ---- per-variant placement ------------------------------------------------------------------------
-// The _placed kernels with an offset table and masks PER VARIANT: place is [nvar][nobj][frames][2], masks are
-// [nvar][nobj][frames][mask_h][mask_w] (variant k's masks in ITS destination coordinates).  Variant k reads object j of frame f
-// at (py - dfy, px - dfx) from row (k * nobj + j) * frames + f.  The variant loop is the OUTER loop and only one variant's NOBJ
-// object vectors are live at a time; next to them the kernels keep the base vector and the loop state, so they need more
-// registers than the _placed kernels (tokens 26 / 39 / 52 / 62 VGPRs against 18 / 26 / 32 / 37, nchw<8> 40 / 112 / 132 / 154 against
-// 30 / 78 / 94 / 110; no scratch; DESIGN.md 6l has the table and what it costs).  With base_chunk0 the base vector
-// is loaded once per work item and every injecting variant blends it with its own objects (the blend differs per variant, so
-// it cannot be shared as in the kernels above); otherwise variant k's base is its own cond chunk.  The arithmetic per variant
-// is blend16_h in object order, absent = (0, 0) entering the arithmetic.  Kernels of their own.
-template <int NOBJ>
-__global__ __launch_bounds__(256) void pnp_tokens_placed_variants_kernel(const PnpArgs p, const int nvar, const unsigned active,
-                                                                         const int* __restrict__ place) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= p.total) return;
-  half_t* x = p.x[blockIdx.y];
-  const int c8n = p.channels >> 3;
-  const int c8 = (int)(idx % c8n);
-  const long fp = idx / c8n;
-  const int hw = p.height * p.width;
-  const int f = (int)(fp / hw), px = (int)(fp % hw);
-  const int py = px / p.width, pxx = px - py * p.width;
-  const int my = nearest_src(py, p.sy, p.mask_h), mx = nearest_src(pxx, p.sx, p.mask_w);
-  const long foff = (long)f * p.f_stride + c8 * 8;
-  const long off = foff + (long)px * p.p_stride;
-  const long mvar = (long)NOBJ * p.frames * p.mask_h * p.mask_w;  // masks of one variant
-  half8_t bv;
-  if (p.base_chunk0) bv = *reinterpret_cast<const half8_t*>(x + off);
-  for (int k = 0; k < nvar; ++k) {
-    if (!((active >> k) & 1u)) continue;
-    const int* pl = place + (long)k * NOBJ * p.frames * 2;
-    const half_t* mk = p.masks + k * mvar;
-    half8_t ov[NOBJ];
-    half_t m[NOBJ];
-#pragma unroll
-    for (int j = 0; j < NOBJ; ++j) {
-      long spix;
-      const bool in = placed_src(pl, j, p.frames, f, py, pxx, p.height, p.width, spix);
-      m[j] = (half_t)0.0f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) ov[j][e] = (half_t)0.0f;
-      if (in) {
-        m[j] = mk[(((long)j * p.frames + f) * p.mask_h + my) * p.mask_w + mx];
-        ov[j] = *reinterpret_cast<const half8_t*>(x + obj_chunk<true>(p, j) * p.chunk_stride + foff + spix * p.p_stride);
-      }
-    }
-    half_t* cond = x + var_dst(p, nvar, p.ndst - 1, k) * p.chunk_stride + off;
-    if (!p.base_chunk0) bv = *reinterpret_cast<const half8_t*>(cond);
-    half8_t o;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      half_t inj = bv[e];
-#pragma unroll
-      for (int j = 0; j < NOBJ; ++j) inj = blend16_h(inj, ov[j][e], m[j]);
-      o[e] = inj;
-    }
-    if (p.ndst == 2) *reinterpret_cast<half8_t*>(x + var_dst(p, nvar, 0, k) * p.chunk_stride + off) = o;
-    *reinterpret_cast<half8_t*>(cond) = o;
-  }
-}
-
-// NCHW: object values one pixel at a time (as pnp_nchw_placed_kernel); base and destinations vectorised when VEC == 8
-template <int VEC, int NOBJ>
-__global__ __launch_bounds__(256) void pnp_nchw_placed_variants_kernel(const PnpArgs p, const int nvar, const unsigned active,
-                                                                       const int* __restrict__ place) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= p.total) return;
-  half_t* x = p.x[blockIdx.y];
-  const int hw = p.height * p.width;
-  const int pvn = hw / VEC;
-  const int pv = (int)(idx % pvn);
-  const long fc = idx / pvn;
-  const int f = (int)(fc / p.channels);
-  const long off = fc * hw + (long)pv * VEC;  // (f*C + c)*HW + p
-  const long chunk = (long)p.frames * p.channels * hw;
-  const long mvar = (long)NOBJ * p.frames * p.mask_h * p.mask_w;  // masks of one variant
-  half_t base[VEC];
-  if (p.base_chunk0) ld_vec<VEC>(base, x + off);
-  for (int k = 0; k < nvar; ++k) {
-    if (!((active >> k) & 1u)) continue;
-    const int* pl = place + (long)k * NOBJ * p.frames * 2;
-    const half_t* mk = p.masks + k * mvar;
-    // The per-pixel terms (row / column, mask index, 64-bit bases) do not depend on k; hoisted out of the variant loop they
-    // stay live across it (202 VGPRs at NOBJ = 4, VEC = 8).  The empty asm makes pv opaque per iteration, so they are formed
-    // inside the loop like the object values (154).
-    int pvk = pv;
-    asm volatile("" : "+v"(pvk));
-    half_t ov[NOBJ][VEC];
-    half_t m[NOBJ][VEC];
-#pragma unroll
-    for (int j = 0; j < NOBJ; ++j) {
-      const half_t* src = x + obj_chunk<true>(p, j) * chunk + fc * hw;
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) {
-        const int px = pvk * VEC + e;
-        const int py = px / p.width, pxx = px - py * p.width;
-        long spix;
-        const bool in = placed_src(pl, j, p.frames, f, py, pxx, p.height, p.width, spix);
-        m[j][e] = (half_t)0.0f;
-        ov[j][e] = (half_t)0.0f;
-        if (in) {
-          const int my = nearest_src(py, p.sy, p.mask_h), mx = nearest_src(pxx, p.sx, p.mask_w);
-          m[j][e] = mk[(((long)j * p.frames + f) * p.mask_h + my) * p.mask_w + mx];
-          ov[j][e] = src[spix];
-        }
-      }
-    }
-    half_t* cond = x + var_dst(p, nvar, p.ndst - 1, k) * chunk + off;
-    if (!p.base_chunk0) ld_vec<VEC>(base, cond);
-    half_t tmp[VEC];
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-      half_t inj = base[e];
-#pragma unroll
-      for (int j = 0; j < NOBJ; ++j) inj = blend16_h(inj, ov[j][e], m[j][e]);
-      tmp[e] = inj;
-    }
-    if (p.ndst == 2) st_vec<VEC>(x + var_dst(p, nvar, 0, k) * chunk + off, tmp);
-    st_vec<VEC>(cond, tmp);
-  }
-}
-
-// ---- scale and mirror: nearest resampling through per-axis index maps ---------------------------------------
-// The _placed kernels with a gather in place of the shift: object j of frame f is read at the pixel (ymap[py], xmap[px]), the
-// maps taken from row j * frames + f of maps = int32 [nobj][frames][height + width] (ymap first, then xmap) -- a device table
-// for THIS site's H x W, constant for the whole call.  The kernels cannot see who wrote the table: an entry is compared UNSIGNED
-// against height / width, anything outside (every negative value included) means the object is absent there, and the source pixel
-// is formed in 64 bits.  Absent = value 0 and mask 0 entering blend16_h, as in the _placed kernels; the masks are in destination
-// coordinates and sampled at the destination pixel.  Kernels of their own, so the instantiations above compile as they always did.
+// MAP: maps = int32 [nobj][frames][height + width] (ymap first, then xmap) -- a device table for THIS site's H x W, constant for
+// the whole call.  The kernels cannot see who wrote the table: an entry is compared UNSIGNED against height / width, anything
+// outside (every negative value included) means the object is absent there, and the source pixel is formed in 64 bits.
 __device__ __forceinline__ bool resampled_src(const int* __restrict__ maps, int j, int frames, int f, int py, int px, int h, int w,
                                               long& spix) {
   const int* mp = maps + ((long)j * frames + f) * ((long)h + w);
@@ -645,126 +201,276 @@ __device__ __forceinline__ bool resampled_src(const int* __restrict__ maps, int 
   return sy < (unsigned)h && sx < (unsigned)w;
 }
 
-template <int NOBJ>
-__global__ __launch_bounds__(256) void pnp_tokens_resampled_kernel(const PnpArgs p, const int nvar, const unsigned active,
-                                                                   const int* __restrict__ maps) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= p.total) return;
-  half_t* x = p.x[blockIdx.y];
-  const int c8n = p.channels >> 3;
-  const int c8 = (int)(idx % c8n);
-  const long fp = idx / c8n;
-  const int hw = p.height * p.width;
-  const int f = (int)(fp / hw), px = (int)(fp % hw);
-  const int py = px / p.width, pxx = px - py * p.width;
-  const int my = nearest_src(py, p.sy, p.mask_h), mx = nearest_src(pxx, p.sx, p.mask_w);
-  const long foff = (long)f * p.f_stride + c8 * 8;
-  const long off = foff + (long)px * p.p_stride;
-  half8_t ov[NOBJ];
-  half_t m[NOBJ];
+enum Src { DIRECT, SHIFT, MAP };
+
+template <Src S>
+__device__ __forceinline__ bool obj_src(const int* __restrict__ tab, int j, int frames, int f, int py, int px, int h, int w,
+                                        long& spix) {
+  if constexpr (S == SHIFT) return placed_src(tab, j, frames, f, py, px, h, w, spix);
+  else return resampled_src(tab, j, frames, f, py, px, h, w, spix);
+}
+
+// NOBJ object vectors of W elements with NM mask values each (tokens: one pixel, NM = 1; NCHW: one per pixel)
+template <Src S, int NOBJ, int W, int NM>
+struct Objs {
+  half_t v[NOBJ][W];
+  std::conditional_t<S == DIRECT, float, half_t> m[NOBJ][NM];
+};
+
+template <Src S, int NOBJ, int W, int NM>
+__device__ __forceinline__ void blend(const half_t (&base)[W], const Objs<S, NOBJ, W, NM>& o, half_t (&out)[W]) {
 #pragma unroll
-  for (int j = 0; j < NOBJ; ++j) {
-    long spix;
-    const bool in = resampled_src(maps, j, p.frames, f, py, pxx, p.height, p.width, spix);
-    m[j] = (half_t)0.0f;
+  for (int e = 0; e < W; ++e) {
+    if constexpr (S == DIRECT) {
+      float inj = (float)base[e];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) ov[j][e] = (half_t)0.0f;
-    if (in) {
-      m[j] = p.masks[(((long)j * p.frames + f) * p.mask_h + my) * p.mask_w + mx];
-      ov[j] = *reinterpret_cast<const half8_t*>(x + obj_chunk<true>(p, j) * p.chunk_stride + foff + spix * p.p_stride);
+      for (int j = 0; j < NOBJ; ++j) inj = blend16(inj, (float)o.v[j][e], o.m[j][NM == 1 ? 0 : e]);
+      out[e] = (half_t)inj;
+    } else {
+      half_t inj = base[e];
+#pragma unroll
+      for (int j = 0; j < NOBJ; ++j) inj = blend16_h(inj, o.v[j][e], o.m[j][NM == 1 ? 0 : e]);
+      out[e] = inj;
     }
-  }
-  half8_t o;
-  if (p.base_chunk0) {  // one blend for every injecting variant
-    const half8_t bv = *reinterpret_cast<const half8_t*>(x + off);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      half_t inj = bv[e];
-#pragma unroll
-      for (int j = 0; j < NOBJ; ++j) inj = blend16_h(inj, ov[j][e], m[j]);
-      o[e] = inj;
-    }
-  }
-  for (int k = 0; k < nvar; ++k) {
-    if (!((active >> k) & 1u)) continue;
-    half_t* cond = x + var_dst(p, nvar, p.ndst - 1, k) * p.chunk_stride + off;
-    if (!p.base_chunk0) {
-      const half8_t bv = *reinterpret_cast<const half8_t*>(cond);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        half_t inj = bv[e];
-#pragma unroll
-        for (int j = 0; j < NOBJ; ++j) inj = blend16_h(inj, ov[j][e], m[j]);
-        o[e] = inj;
-      }
-    }
-    if (p.ndst == 2) *reinterpret_cast<half8_t*>(x + var_dst(p, nvar, 0, k) * p.chunk_stride + off) = o;
-    *reinterpret_cast<half8_t*>(cond) = o;
   }
 }
 
-// NCHW: object values one pixel at a time (each of the VEC pixels of a work item has its own source pixel, and under a scale
-// neighbouring destinations no longer read neighbouring sources); base and destinations vectorised when VEC == 8
+__device__ __forceinline__ long mask_index(const PnpArgs& p, int j, int f, int my, int mx) {
+  return (((long)j * p.frames + f) * p.mask_h + my) * p.mask_w + mx;
+}
+
+// tokens: item = (f, p, c8), 8 consecutive channels of one (frame, pixel)
+struct Tokens {
+  static constexpr int W = 8, NM = 1;
+  int f, py, px, my, mx;
+  long foff, off, chunk;  // foff: the item's frame and channels, off: + its pixel; chunk stride
+
+  __device__ __forceinline__ bool init(const PnpArgs& p) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= p.total) return false;
+    const int c8n = p.channels >> 3;
+    const int c8 = (int)(idx % c8n);
+    const long fp = idx / c8n;
+    const int hw = p.height * p.width;
+    f = (int)(fp / hw);
+    const int pix = (int)(fp % hw);
+    py = pix / p.width, px = pix - py * p.width;
+    my = nearest_src(py, p.sy, p.mask_h), mx = nearest_src(px, p.sx, p.mask_w);
+    foff = (long)f * p.f_stride + c8 * 8;
+    off = foff + (long)pix * p.p_stride;
+    chunk = p.chunk_stride;
+    return true;
+  }
+
+  __device__ __forceinline__ Tokens per_variant() const { return *this; }
+
+  template <Src S, int NOBJ>
+  __device__ __forceinline__ void load(const PnpArgs& p, const half_t* x, const half_t* masks, const int* __restrict__ tab,
+                                       Objs<S, NOBJ, 8, 1>& o) const {
+#pragma unroll
+    for (int j = 0; j < NOBJ; ++j) {
+      const half_t* src = x + obj_chunk<true>(p, j) * chunk;
+      if constexpr (S == DIRECT) {
+        o.m[j][0] = (float)masks[mask_index(p, j, f, my, mx)];
+        ld_vec<8>(o.v[j], src + off);
+      } else {
+        long spix;
+        const bool in = obj_src<S>(tab, j, p.frames, f, py, px, p.height, p.width, spix);
+        o.m[j][0] = (half_t)0.0f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o.v[j][e] = (half_t)0.0f;
+        if (in) {
+          o.m[j][0] = masks[mask_index(p, j, f, my, mx)];
+          ld_vec<8>(o.v[j], src + foff + spix * p.p_stride);
+        }
+      }
+    }
+  }
+};
+
+// NCHW: x [chunks * F, C, H, W]; item = (f, c, pv) with VEC consecutive pixels.  SHIFT / MAP read the object values one pixel at
+// a time: a shift in x breaks the 8-pixel alignment of the object rows and under a scale neighbouring destinations no longer read
+// neighbouring sources, so each of the VEC pixels has its own source pixel; the base and the destinations keep the vector accesses
+template <int VEC>
+struct Nchw {
+  static constexpr int W = VEC, NM = VEC;
+  int f, pv;
+  long plane, off, chunk;  // plane: (f*C + c)*HW, off: + the item's first pixel; chunk stride
+
+  __device__ __forceinline__ bool init(const PnpArgs& p) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= p.total) return false;
+    const int hw = p.height * p.width;
+    const int pvn = hw / VEC;
+    pv = (int)(idx % pvn);
+    const long fc = idx / pvn;
+    f = (int)(fc / p.channels);
+    plane = fc * hw;
+    off = plane + (long)pv * VEC;
+    chunk = (long)p.frames * p.channels * hw;
+    return true;
+  }
+
+  // The per-pixel terms of a load (row / column, mask index, 64-bit bases) do not depend on the variant; hoisted out of the
+  // variant loop of blend_scatter_per_variant they stay live across it (202 VGPRs at NOBJ = 4, VEC = 8).  The empty asm makes
+  // pv opaque per iteration, so they are formed inside the loop like the object values (154).
+  __device__ __forceinline__ Nchw per_variant() const {
+    Nchw it = *this;
+    asm volatile("" : "+v"(it.pv));
+    return it;
+  }
+
+  template <Src S, int NOBJ>
+  __device__ __forceinline__ void load(const PnpArgs& p, const half_t* x, const half_t* masks, const int* __restrict__ tab,
+                                       Objs<S, NOBJ, VEC, VEC>& o) const {
+    if constexpr (S == DIRECT) {
+      // The pixels' offsets inside one mask plane are formed ONCE, outside the object loop, and object j adds its plane: left
+      // inside, hipcc forms the whole 64-bit index per (object, pixel) and the <8, 2..4> instantiations sit at or above their
+      // occupancy steps (64 / 64 / 80 VGPRs and more); this way they need 46 / 60 / 66.  The masks are read before the vector.
+      long mpix[VEC];
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        const int pix = pv * VEC + e;
+        const int py = pix / p.width, px = pix - py * p.width;
+        mpix[e] = (long)nearest_src(py, p.sy, p.mask_h) * p.mask_w + nearest_src(px, p.sx, p.mask_w);
+      }
+#pragma unroll
+      for (int j = 0; j < NOBJ; ++j) {
+        const half_t* mj = masks + ((long)j * p.frames + f) * ((long)p.mask_h * p.mask_w);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) o.m[j][e] = (float)mj[mpix[e]];
+        ld_vec<VEC>(o.v[j], x + obj_chunk<true>(p, j) * chunk + off);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < NOBJ; ++j) {
+        const half_t* src = x + obj_chunk<true>(p, j) * chunk + plane;
+        const long mrow = ((long)j * p.frames + f) * p.mask_h;  // first mask row of (object, frame)
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+          const int pix = pv * VEC + e;
+          const int py = pix / p.width, px = pix - py * p.width;
+          long spix;
+          const bool in = obj_src<S>(tab, j, p.frames, f, py, px, p.height, p.width, spix);
+          o.m[j][e] = (half_t)0.0f;
+          o.v[j][e] = (half_t)0.0f;
+          if (in) {
+            const int my = nearest_src(py, p.sy, p.mask_h), mx = nearest_src(px, p.sx, p.mask_w);
+            o.m[j][e] = masks[(mrow + my) * p.mask_w + mx];
+            o.v[j][e] = src[spix];
+          }
+        }
+      }
+    }
+  }
+};
+
+template <class L, Src S, bool SEL, int NOBJ>
+__device__ __forceinline__ void blend_scatter(const PnpArgs& p, int nvar, unsigned active, const int* __restrict__ tab) {
+  L it;
+  if (!it.init(p)) return;
+  half_t* x = p.x[blockIdx.y];
+  Objs<S, NOBJ, L::W, L::NM> o;
+  it.template load<S, NOBJ>(p, x, p.masks, tab, o);
+  half_t t[L::W];
+  if (p.base_chunk0) {  // one blend for every injecting variant
+    ld_vec<L::W>(t, x + it.off);
+    blend(t, o, t);
+  }
+  for (int k = 0; k < nvar; ++k) {
+    if constexpr (SEL)
+      if (!((active >> k) & 1u)) continue;
+    half_t* cond = x + var_dst(p, nvar, p.ndst - 1, k) * it.chunk + it.off;
+    if (!p.base_chunk0) {
+      ld_vec<L::W>(t, cond);
+      blend(t, o, t);
+    }
+    if (p.ndst == 2) st_vec<L::W>(x + var_dst(p, nvar, 0, k) * it.chunk + it.off, t);
+    st_vec<L::W>(cond, t);
+  }
+}
+
+// An offset table and masks PER VARIANT: place is [nvar][nobj][frames][2], masks are [nvar][nobj][frames][mask_h][mask_w]
+// (variant k's masks in ITS destination coordinates).  The variant loop is the OUTER loop and only one variant's NOBJ object
+// vectors are live at a time; next to them the kernels keep the base vector and the loop state, so they need more registers
+// than the _placed kernels (DESIGN.md 6l has the table and what it costs).  With base_chunk0 the base vector is loaded once per
+// work item and every injecting variant blends it with its own objects (the blend differs per variant, so it cannot be shared
+// as in blend_scatter); otherwise variant k's base is its own cond chunk.
+template <class L, int NOBJ>
+__device__ __forceinline__ void blend_scatter_per_variant(const PnpArgs& p, int nvar, unsigned active, const int* __restrict__ place) {
+  L it;
+  if (!it.init(p)) return;
+  half_t* x = p.x[blockIdx.y];
+  const long mvar = (long)NOBJ * p.frames * p.mask_h * p.mask_w;  // masks of one variant
+  half_t base[L::W];
+  if (p.base_chunk0) ld_vec<L::W>(base, x + it.off);
+  for (int k = 0; k < nvar; ++k) {
+    if (!((active >> k) & 1u)) continue;
+    Objs<SHIFT, NOBJ, L::W, L::NM> o;
+    it.per_variant().template load<SHIFT, NOBJ>(p, x, p.masks + k * mvar, place + (long)k * NOBJ * p.frames * 2, o);
+    half_t* cond = x + var_dst(p, nvar, p.ndst - 1, k) * it.chunk + it.off;
+    if (!p.base_chunk0) ld_vec<L::W>(base, cond);
+    half_t t[L::W];
+    blend(base, o, t);
+    if (p.ndst == 2) st_vec<L::W>(x + var_dst(p, nvar, 0, k) * it.chunk + it.off, t);
+    st_vec<L::W>(cond, t);
+  }
+}
+
+template <int NOBJ>
+__global__ __launch_bounds__(256) void pnp_tokens_variants_kernel(const PnpArgs p, const int nvar) {
+  blend_scatter<Tokens, DIRECT, false, NOBJ>(p, nvar, 0u, nullptr);
+}
+
+template <int VEC, int NOBJ>
+__global__ __launch_bounds__(256) void pnp_nchw_variants_kernel(const PnpArgs p, const int nvar) {
+  blend_scatter<Nchw<VEC>, DIRECT, false, NOBJ>(p, nvar, 0u, nullptr);
+}
+
+template <int NOBJ>
+__global__ __launch_bounds__(256) void pnp_tokens_variants_sel_kernel(const PnpArgs p, const int nvar, const unsigned active) {
+  blend_scatter<Tokens, DIRECT, true, NOBJ>(p, nvar, active, nullptr);
+}
+
+template <int VEC, int NOBJ>
+__global__ __launch_bounds__(256) void pnp_nchw_variants_sel_kernel(const PnpArgs p, const int nvar, const unsigned active) {
+  blend_scatter<Nchw<VEC>, DIRECT, true, NOBJ>(p, nvar, active, nullptr);
+}
+
+template <int NOBJ>
+__global__ __launch_bounds__(256) void pnp_tokens_placed_kernel(const PnpArgs p, const int nvar, const unsigned active,
+                                                                const int* __restrict__ place) {
+  blend_scatter<Tokens, SHIFT, true, NOBJ>(p, nvar, active, place);
+}
+
+template <int VEC, int NOBJ>
+__global__ __launch_bounds__(256) void pnp_nchw_placed_kernel(const PnpArgs p, const int nvar, const unsigned active,
+                                                              const int* __restrict__ place) {
+  blend_scatter<Nchw<VEC>, SHIFT, true, NOBJ>(p, nvar, active, place);
+}
+
+template <int NOBJ>
+__global__ __launch_bounds__(256) void pnp_tokens_placed_variants_kernel(const PnpArgs p, const int nvar, const unsigned active,
+                                                                         const int* __restrict__ place) {
+  blend_scatter_per_variant<Tokens, NOBJ>(p, nvar, active, place);
+}
+
+template <int VEC, int NOBJ>
+__global__ __launch_bounds__(256) void pnp_nchw_placed_variants_kernel(const PnpArgs p, const int nvar, const unsigned active,
+                                                                       const int* __restrict__ place) {
+  blend_scatter_per_variant<Nchw<VEC>, NOBJ>(p, nvar, active, place);
+}
+
+template <int NOBJ>
+__global__ __launch_bounds__(256) void pnp_tokens_resampled_kernel(const PnpArgs p, const int nvar, const unsigned active,
+                                                                   const int* __restrict__ maps) {
+  blend_scatter<Tokens, MAP, true, NOBJ>(p, nvar, active, maps);
+}
+
 template <int VEC, int NOBJ>
 __global__ __launch_bounds__(256) void pnp_nchw_resampled_kernel(const PnpArgs p, const int nvar, const unsigned active,
                                                                  const int* __restrict__ maps) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= p.total) return;
-  half_t* x = p.x[blockIdx.y];
-  const int hw = p.height * p.width;
-  const int pvn = hw / VEC;
-  const int pv = (int)(idx % pvn);
-  const long fc = idx / pvn;
-  const int f = (int)(fc / p.channels);
-  const long off = fc * hw + (long)pv * VEC;  // (f*C + c)*HW + p
-  const long chunk = (long)p.frames * p.channels * hw;
-  half_t ov[NOBJ][VEC];
-  half_t m[NOBJ][VEC];
-#pragma unroll
-  for (int j = 0; j < NOBJ; ++j) {
-    const half_t* src = x + obj_chunk<true>(p, j) * chunk + fc * hw;
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-      const int px = pv * VEC + e;
-      const int py = px / p.width, pxx = px - py * p.width;
-      long spix;
-      const bool in = resampled_src(maps, j, p.frames, f, py, pxx, p.height, p.width, spix);
-      m[j][e] = (half_t)0.0f;
-      ov[j][e] = (half_t)0.0f;
-      if (in) {
-        const int my = nearest_src(py, p.sy, p.mask_h), mx = nearest_src(pxx, p.sx, p.mask_w);
-        m[j][e] = p.masks[(((long)j * p.frames + f) * p.mask_h + my) * p.mask_w + mx];
-        ov[j][e] = src[spix];
-      }
-    }
-  }
-  half_t tmp[VEC];
-  if (p.base_chunk0) {
-    ld_vec<VEC>(tmp, x + off);
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-      half_t inj = tmp[e];
-#pragma unroll
-      for (int j = 0; j < NOBJ; ++j) inj = blend16_h(inj, ov[j][e], m[j][e]);
-      tmp[e] = inj;
-    }
-  }
-  for (int k = 0; k < nvar; ++k) {
-    if (!((active >> k) & 1u)) continue;
-    half_t* cond = x + var_dst(p, nvar, p.ndst - 1, k) * chunk + off;
-    if (!p.base_chunk0) {
-      ld_vec<VEC>(tmp, cond);
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) {
-        half_t inj = tmp[e];
-#pragma unroll
-        for (int j = 0; j < NOBJ; ++j) inj = blend16_h(inj, ov[j][e], m[j][e]);
-        tmp[e] = inj;
-      }
-    }
-    if (p.ndst == 2) st_vec<VEC>(x + var_dst(p, nvar, 0, k) * chunk + off, tmp);
-    st_vec<VEC>(cond, tmp);
-  }
+  blend_scatter<Nchw<VEC>, MAP, true, NOBJ>(p, nvar, active, maps);
 }
 
 // zero-filled per-frame gather of [nplane][F][h][w]: dst[pl, f, y, x] = src[pl, f, ymap_f[y], xmap_f[x]] or 0 where either
@@ -939,115 +645,87 @@ __global__ __launch_bounds__(256) void fusion_variants_kernel(const half_t* __re
   out[i] = (half_t)l;
 }
 
-}  // namespace
+// ---- host launch of the blend family ------------------------------------------------------------------------------------------
+// What every entry of a layout derives from the descriptor: prepare_* checks the layout's preconditions, sets a.total and fills
+// this; blend_bytes is the traffic the entry reports to the profiler; dispatch picks the instantiation.
+struct Launch {
+  dim3 grid;
+  hipStream_t s;
+  int ntens;
+  bool vec;              // nchw: 8 pixels per work item (H * W a multiple of 8); tokens: always 8 channels
+  double elems, pixels;  // F * H * W * C and F * H * W
+};
 
-namespace {
+int finish_prepare(const mvoc_pnp_desc* d, const PnpArgs& a, void* stream, Launch& l, const char* too_large) {
+  const long nblk = (a.total + 255) / 256;
+  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "%s", too_large);
+  l.ntens = d->x2 ? 2 : 1;
+  l.grid = dim3((unsigned)nblk, l.ntens);
+  l.s = (hipStream_t)stream;
+  l.pixels = (double)d->frames * d->height * d->width;
+  l.elems = l.pixels * d->channels;
+  return 0;
+}
+
+int prepare_tokens(const mvoc_pnp_desc* d, PnpArgs& a, void* stream, Launch& l) {
+  MVOC_REQUIRE(d->channels % 8 == 0 && d->chunk_stride % 8 == 0 && d->f_stride % 8 == 0 && d->p_stride % 8 == 0, -2,
+               "pnp tokens: channels/strides must be multiples of 8");
+  l.vec = true;
+  a.total = (long)d->frames * d->height * d->width * (d->channels / 8);
+  return finish_prepare(d, a, stream, l, "pnp tokens: grid too large");
+}
+
+int prepare_nchw(const mvoc_pnp_desc* d, PnpArgs& a, void* stream, Launch& l) {
+  const long hw = (long)d->height * d->width;
+  l.vec = hw % 8 == 0;
+  a.total = (long)d->frames * d->channels * (l.vec ? hw / 8 : hw);
+  return finish_prepare(d, a, stream, l, "pnp nchw: grid too large");
+}
+
+// per tensor: `chunks` chunks of features read or written + `mask_sets` sets of nobj masks; + the bytes of a device table
+double blend_bytes(const Launch& l, int nobj, double chunks, double mask_sets = 1.0, double table = 0.0) {
+  return l.ntens * (l.elems * 2.0 * chunks + 2.0 * mask_sets * nobj * l.pixels) + table;
+}
+
+// f(NOBJ, VEC) as integral constants: nobj in [1, 4] (fill_args), VEC = 8 or 1 (the tokens kernels have no VEC and ignore it)
+template <class F>
+void dispatch(int nobj, bool vec, F&& f) {
+  auto by_vec = [&](auto n) {
+    if (vec) f(n, std::integral_constant<int, 8>{});
+    else f(n, std::integral_constant<int, 1>{});
+  };
+  switch (nobj) {
+    case 1: by_vec(std::integral_constant<int, 1>{}); break;
+    case 2: by_vec(std::integral_constant<int, 2>{}); break;
+    case 3: by_vec(std::integral_constant<int, 3>{}); break;
+    default: by_vec(std::integral_constant<int, 4>{}); break;
+  }
+}
+
+template <class K, class... Args>
+void launch(K kernel, const Launch& l, Args... args) {
+  hipLaunchKernelGGL(kernel, l.grid, dim3(256), 0, l.s, args...);
+}
 
 // nread: source chunks read from HBM (the base included); ndst chunks written
 template <bool MAPPED>
 int launch_tokens(const mvoc_pnp_desc* d, PnpArgs& a, int nread, void* stream) {
-  MVOC_REQUIRE(d->channels % 8 == 0 && d->chunk_stride % 8 == 0 && d->f_stride % 8 == 0 && d->p_stride % 8 == 0, -2,
-               "pnp tokens: channels/strides must be multiples of 8");
-  a.total = (long)d->frames * d->height * d->width * (d->channels / 8);
-  const long nblk = (a.total + 255) / 256;
-  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "pnp tokens: grid too large");
-  const int ntens = d->x2 ? 2 : 1;
-  hipStream_t s = (hipStream_t)stream;
-  const double elems = (double)d->frames * d->height * d->width * d->channels;
-  MvocProfScope prof(MVOC_FAM_PNP, s, ntens * (elems * 2.0 * (nread + a.ndst) + 2.0 * d->nobj * d->frames * d->height * d->width));
-  hipLaunchKernelGGL(pnp_tokens_kernel<MAPPED>, dim3((unsigned)nblk, ntens), dim3(256), 0, s, a);
+  Launch l;
+  if (int rc = prepare_tokens(d, a, stream, l)) return rc;
+  MvocProfScope prof(MVOC_FAM_PNP, l.s, blend_bytes(l, d->nobj, nread + a.ndst));
+  launch(pnp_tokens_kernel<MAPPED>, l, a);
   return mvoc_check_launch("pnp_tokens_kernel");
 }
 
 template <bool MAPPED>
 int launch_nchw(const mvoc_pnp_desc* d, PnpArgs& a, int nread, void* stream) {
-  const long hw = (long)d->height * d->width;
-  const bool vec = hw % 8 == 0;
-  a.total = (long)d->frames * d->channels * (vec ? hw / 8 : hw);
-  const long nblk = (a.total + 255) / 256;
-  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "pnp nchw: grid too large");
-  const int ntens = d->x2 ? 2 : 1;
-  hipStream_t s = (hipStream_t)stream;
-  const double elems = (double)d->frames * hw * d->channels;
-  MvocProfScope prof(MVOC_FAM_PNP, s, ntens * (elems * 2.0 * (nread + a.ndst) + 2.0 * d->nobj * d->frames * hw));
-  if (vec)
-    hipLaunchKernelGGL((pnp_nchw_kernel<8, MAPPED>), dim3((unsigned)nblk, ntens), dim3(256), 0, s, a);
-  else
-    hipLaunchKernelGGL((pnp_nchw_kernel<1, MAPPED>), dim3((unsigned)nblk, ntens), dim3(256), 0, s, a);
+  Launch l;
+  if (int rc = prepare_nchw(d, a, stream, l)) return rc;
+  MvocProfScope prof(MVOC_FAM_PNP, l.s, blend_bytes(l, d->nobj, nread + a.ndst));
+  if (l.vec) launch(pnp_nchw_kernel<8, MAPPED>, l, a);
+  else launch(pnp_nchw_kernel<1, MAPPED>, l, a);
   return mvoc_check_launch("pnp_nchw_kernel");
 }
-
-// variants: nsrc_read distinct source chunks read (+ K bases unless the base is chunk 0), ndst * K chunks written
-int fill_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar, PnpArgs& a, double& chunks) {
-  MVOC_REQUIRE(nvar >= 1 && nvar <= 8, -1, "pnp variants: nvar %d not in [1, 8]", nvar);
-  int nread = 0;
-  if (int rc = fill_args(d, a)) return rc;
-  if (int rc = fill_map(d, nsrc, obj_chunk, a, nread)) return rc;
-  chunks = (d->base_chunk0 ? nread : nread - 1 + nvar) + (double)a.ndst * nvar;
-  return 0;
-}
-
-template <int NOBJ>
-void launch_nchw_variants_n(bool vec, dim3 grid, hipStream_t s, const PnpArgs& a, int nvar) {
-  if (vec)
-    hipLaunchKernelGGL((pnp_nchw_variants_kernel<8, NOBJ>), grid, dim3(256), 0, s, a, nvar);
-  else
-    hipLaunchKernelGGL((pnp_nchw_variants_kernel<1, NOBJ>), grid, dim3(256), 0, s, a, nvar);
-}
-
-}  // namespace
-
-extern "C" int mvoc_pnp_blend_scatter_tokens_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
-                                                      int32_t nvar, void* stream) {
-  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_tokens_variants")) return rc;
-  PnpArgs a;
-  double chunks = 0;
-  if (int rc = fill_variants(d, nsrc, obj_chunk, nvar, a, chunks)) return rc;
-  MVOC_REQUIRE(d->channels % 8 == 0 && d->chunk_stride % 8 == 0 && d->f_stride % 8 == 0 && d->p_stride % 8 == 0, -2,
-               "pnp tokens: channels/strides must be multiples of 8");
-  a.total = (long)d->frames * d->height * d->width * (d->channels / 8);
-  const long nblk = (a.total + 255) / 256;
-  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "pnp tokens: grid too large");
-  const int ntens = d->x2 ? 2 : 1;
-  hipStream_t s = (hipStream_t)stream;
-  const double elems = (double)d->frames * d->height * d->width * d->channels;
-  MvocProfScope prof(MVOC_FAM_PNP, s, ntens * (elems * 2.0 * chunks + 2.0 * d->nobj * d->frames * d->height * d->width));
-  const dim3 grid((unsigned)nblk, ntens);
-  switch (d->nobj) {
-    case 1: hipLaunchKernelGGL(pnp_tokens_variants_kernel<1>, grid, dim3(256), 0, s, a, (int)nvar); break;
-    case 2: hipLaunchKernelGGL(pnp_tokens_variants_kernel<2>, grid, dim3(256), 0, s, a, (int)nvar); break;
-    case 3: hipLaunchKernelGGL(pnp_tokens_variants_kernel<3>, grid, dim3(256), 0, s, a, (int)nvar); break;
-    default: hipLaunchKernelGGL(pnp_tokens_variants_kernel<4>, grid, dim3(256), 0, s, a, (int)nvar); break;
-  }
-  return mvoc_check_launch("pnp_tokens_variants_kernel");
-}
-
-extern "C" int mvoc_pnp_blend_scatter_nchw_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
-                                                    int32_t nvar, void* stream) {
-  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_nchw_variants")) return rc;
-  PnpArgs a;
-  double chunks = 0;
-  if (int rc = fill_variants(d, nsrc, obj_chunk, nvar, a, chunks)) return rc;
-  const long hw = (long)d->height * d->width;
-  const bool vec = hw % 8 == 0;
-  a.total = (long)d->frames * d->channels * (vec ? hw / 8 : hw);
-  const long nblk = (a.total + 255) / 256;
-  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "pnp nchw: grid too large");
-  const int ntens = d->x2 ? 2 : 1;
-  hipStream_t s = (hipStream_t)stream;
-  const double elems = (double)d->frames * hw * d->channels;
-  MvocProfScope prof(MVOC_FAM_PNP, s, ntens * (elems * 2.0 * chunks + 2.0 * d->nobj * d->frames * hw));
-  const dim3 grid((unsigned)nblk, ntens);
-  switch (d->nobj) {
-    case 1: launch_nchw_variants_n<1>(vec, grid, s, a, nvar); break;
-    case 2: launch_nchw_variants_n<2>(vec, grid, s, a, nvar); break;
-    case 3: launch_nchw_variants_n<3>(vec, grid, s, a, nvar); break;
-    default: launch_nchw_variants_n<4>(vec, grid, s, a, nvar); break;
-  }
-  return mvoc_check_launch("pnp_nchw_variants_kernel");
-}
-
-namespace {
 
 // _sel: distinct sources read (+ one base per INJECTING variant unless the base is chunk 0), ndst chunks written per injecting variant
 int fill_variants_sel(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar, uint32_t active, PnpArgs& a,
@@ -1063,68 +741,10 @@ int fill_variants_sel(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_c
   return 0;
 }
 
-template <int NOBJ>
-void launch_nchw_variants_sel_n(bool vec, dim3 grid, hipStream_t s, const PnpArgs& a, int nvar, unsigned active) {
-  if (vec)
-    hipLaunchKernelGGL((pnp_nchw_variants_sel_kernel<8, NOBJ>), grid, dim3(256), 0, s, a, nvar, active);
-  else
-    hipLaunchKernelGGL((pnp_nchw_variants_sel_kernel<1, NOBJ>), grid, dim3(256), 0, s, a, nvar, active);
+// variants: every variant injects (an nvar outside [1, 8] is refused before the mask is looked at)
+int fill_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar, PnpArgs& a, double& chunks) {
+  return fill_variants_sel(d, nsrc, obj_chunk, nvar, nvar >= 1 && nvar <= 8 ? (1u << nvar) - 1 : 0u, a, chunks);
 }
-
-}  // namespace
-
-extern "C" int mvoc_pnp_blend_scatter_tokens_variants_sel(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
-                                                          int32_t nvar, uint32_t active, void* stream) {
-  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_tokens_variants_sel")) return rc;
-  PnpArgs a;
-  double chunks = 0;
-  if (int rc = fill_variants_sel(d, nsrc, obj_chunk, nvar, active, a, chunks)) return rc;
-  MVOC_REQUIRE(d->channels % 8 == 0 && d->chunk_stride % 8 == 0 && d->f_stride % 8 == 0 && d->p_stride % 8 == 0, -2,
-               "pnp tokens: channels/strides must be multiples of 8");
-  a.total = (long)d->frames * d->height * d->width * (d->channels / 8);
-  const long nblk = (a.total + 255) / 256;
-  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "pnp tokens: grid too large");
-  const int ntens = d->x2 ? 2 : 1;
-  hipStream_t s = (hipStream_t)stream;
-  const double elems = (double)d->frames * d->height * d->width * d->channels;
-  MvocProfScope prof(MVOC_FAM_PNP, s, ntens * (elems * 2.0 * chunks + 2.0 * d->nobj * d->frames * d->height * d->width));
-  const dim3 grid((unsigned)nblk, ntens);
-  const unsigned act = active;
-  switch (d->nobj) {
-    case 1: hipLaunchKernelGGL(pnp_tokens_variants_sel_kernel<1>, grid, dim3(256), 0, s, a, (int)nvar, act); break;
-    case 2: hipLaunchKernelGGL(pnp_tokens_variants_sel_kernel<2>, grid, dim3(256), 0, s, a, (int)nvar, act); break;
-    case 3: hipLaunchKernelGGL(pnp_tokens_variants_sel_kernel<3>, grid, dim3(256), 0, s, a, (int)nvar, act); break;
-    default: hipLaunchKernelGGL(pnp_tokens_variants_sel_kernel<4>, grid, dim3(256), 0, s, a, (int)nvar, act); break;
-  }
-  return mvoc_check_launch("pnp_tokens_variants_sel_kernel");
-}
-
-extern "C" int mvoc_pnp_blend_scatter_nchw_variants_sel(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
-                                                        int32_t nvar, uint32_t active, void* stream) {
-  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_nchw_variants_sel")) return rc;
-  PnpArgs a;
-  double chunks = 0;
-  if (int rc = fill_variants_sel(d, nsrc, obj_chunk, nvar, active, a, chunks)) return rc;
-  const long hw = (long)d->height * d->width;
-  const bool vec = hw % 8 == 0;
-  a.total = (long)d->frames * d->channels * (vec ? hw / 8 : hw);
-  const long nblk = (a.total + 255) / 256;
-  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "pnp nchw: grid too large");
-  const int ntens = d->x2 ? 2 : 1;
-  hipStream_t s = (hipStream_t)stream;
-  const double elems = (double)d->frames * hw * d->channels;
-  MvocProfScope prof(MVOC_FAM_PNP, s, ntens * (elems * 2.0 * chunks + 2.0 * d->nobj * d->frames * hw));
-  const dim3 grid((unsigned)nblk, ntens);
-  switch (d->nobj) {
-    case 1: launch_nchw_variants_sel_n<1>(vec, grid, s, a, nvar, active); break;
-    case 2: launch_nchw_variants_sel_n<2>(vec, grid, s, a, nvar, active); break;
-    case 3: launch_nchw_variants_sel_n<3>(vec, grid, s, a, nvar, active); break;
-    default: launch_nchw_variants_sel_n<4>(vec, grid, s, a, nvar, active); break;
-  }
-  return mvoc_check_launch("pnp_nchw_variants_sel_kernel");
-}
-
-namespace {
 
 // _placed: the _sel contract (nvar = 1 and every bit of `active` set are allowed) + the device table of feature offsets
 int fill_placed(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar, uint32_t active, const void* place,
@@ -1132,71 +752,6 @@ int fill_placed(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, 
   MVOC_REQUIRE(place, -1, "pnp placed: null offset table");
   return fill_variants_sel(d, nsrc, obj_chunk, nvar, active, a, chunks);
 }
-
-template <int NOBJ>
-void launch_nchw_placed_n(bool vec, dim3 grid, hipStream_t s, const PnpArgs& a, int nvar, unsigned active, const int* place) {
-  if (vec)
-    hipLaunchKernelGGL((pnp_nchw_placed_kernel<8, NOBJ>), grid, dim3(256), 0, s, a, nvar, active, place);
-  else
-    hipLaunchKernelGGL((pnp_nchw_placed_kernel<1, NOBJ>), grid, dim3(256), 0, s, a, nvar, active, place);
-}
-
-}  // namespace
-
-extern "C" int mvoc_pnp_blend_scatter_tokens_placed(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
-                                                    uint32_t active, const int32_t* place, void* stream) {
-  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_tokens_placed")) return rc;
-  PnpArgs a;
-  double chunks = 0;
-  if (int rc = fill_placed(d, nsrc, obj_chunk, nvar, active, place, a, chunks)) return rc;
-  MVOC_REQUIRE(d->channels % 8 == 0 && d->chunk_stride % 8 == 0 && d->f_stride % 8 == 0 && d->p_stride % 8 == 0, -2,
-               "pnp tokens: channels/strides must be multiples of 8");
-  a.total = (long)d->frames * d->height * d->width * (d->channels / 8);
-  const long nblk = (a.total + 255) / 256;
-  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "pnp tokens: grid too large");
-  const int ntens = d->x2 ? 2 : 1;
-  hipStream_t s = (hipStream_t)stream;
-  const double elems = (double)d->frames * d->height * d->width * d->channels;
-  MvocProfScope prof(MVOC_FAM_PNP, s, ntens * (elems * 2.0 * chunks + 2.0 * d->nobj * d->frames * d->height * d->width));
-  const dim3 grid((unsigned)nblk, ntens);
-  const unsigned act = active;
-  const int* pl = (const int*)place;
-  switch (d->nobj) {
-    case 1: hipLaunchKernelGGL(pnp_tokens_placed_kernel<1>, grid, dim3(256), 0, s, a, (int)nvar, act, pl); break;
-    case 2: hipLaunchKernelGGL(pnp_tokens_placed_kernel<2>, grid, dim3(256), 0, s, a, (int)nvar, act, pl); break;
-    case 3: hipLaunchKernelGGL(pnp_tokens_placed_kernel<3>, grid, dim3(256), 0, s, a, (int)nvar, act, pl); break;
-    default: hipLaunchKernelGGL(pnp_tokens_placed_kernel<4>, grid, dim3(256), 0, s, a, (int)nvar, act, pl); break;
-  }
-  return mvoc_check_launch("pnp_tokens_placed_kernel");
-}
-
-extern "C" int mvoc_pnp_blend_scatter_nchw_placed(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
-                                                  uint32_t active, const int32_t* place, void* stream) {
-  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_nchw_placed")) return rc;
-  PnpArgs a;
-  double chunks = 0;
-  if (int rc = fill_placed(d, nsrc, obj_chunk, nvar, active, place, a, chunks)) return rc;
-  const long hw = (long)d->height * d->width;
-  const bool vec = hw % 8 == 0;
-  a.total = (long)d->frames * d->channels * (vec ? hw / 8 : hw);
-  const long nblk = (a.total + 255) / 256;
-  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "pnp nchw: grid too large");
-  const int ntens = d->x2 ? 2 : 1;
-  hipStream_t s = (hipStream_t)stream;
-  const double elems = (double)d->frames * hw * d->channels;
-  MvocProfScope prof(MVOC_FAM_PNP, s, ntens * (elems * 2.0 * chunks + 2.0 * d->nobj * d->frames * hw));
-  const dim3 grid((unsigned)nblk, ntens);
-  const int* pl = (const int*)place;
-  switch (d->nobj) {
-    case 1: launch_nchw_placed_n<1>(vec, grid, s, a, nvar, active, pl); break;
-    case 2: launch_nchw_placed_n<2>(vec, grid, s, a, nvar, active, pl); break;
-    case 3: launch_nchw_placed_n<3>(vec, grid, s, a, nvar, active, pl); break;
-    default: launch_nchw_placed_n<4>(vec, grid, s, a, nvar, active, pl); break;
-  }
-  return mvoc_check_launch("pnp_nchw_placed_kernel");
-}
-
-namespace {
 
 // _placed_variants: the _placed contract with a table and masks per variant.  Traffic in chunks: every injecting variant reads
 // the distinct object chunks at its own pixels (nobjc each) and writes ndst chunks; the base is read once when it is chunk 0,
@@ -1212,77 +767,6 @@ int fill_placed_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* ob
   return 0;
 }
 
-template <int NOBJ>
-void launch_nchw_placed_variants_n(bool vec, dim3 grid, hipStream_t s, const PnpArgs& a, int nvar, unsigned active,
-                                   const int* place) {
-  if (vec)
-    hipLaunchKernelGGL((pnp_nchw_placed_variants_kernel<8, NOBJ>), grid, dim3(256), 0, s, a, nvar, active, place);
-  else
-    hipLaunchKernelGGL((pnp_nchw_placed_variants_kernel<1, NOBJ>), grid, dim3(256), 0, s, a, nvar, active, place);
-}
-
-}  // namespace
-
-extern "C" int mvoc_pnp_blend_scatter_tokens_placed_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
-                                                             int32_t nvar, uint32_t active, const int32_t* place, void* stream) {
-  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_tokens_placed_variants")) return rc;
-  PnpArgs a;
-  double chunks = 0;
-  int on = 0;
-  if (int rc = fill_placed_variants(d, nsrc, obj_chunk, nvar, active, place, a, chunks, on)) return rc;
-  MVOC_REQUIRE(d->channels % 8 == 0 && d->chunk_stride % 8 == 0 && d->f_stride % 8 == 0 && d->p_stride % 8 == 0, -2,
-               "pnp tokens: channels/strides must be multiples of 8");
-  a.total = (long)d->frames * d->height * d->width * (d->channels / 8);
-  const long nblk = (a.total + 255) / 256;
-  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "pnp tokens: grid too large");
-  const int ntens = d->x2 ? 2 : 1;
-  hipStream_t s = (hipStream_t)stream;
-  const double elems = (double)d->frames * d->height * d->width * d->channels;
-  MvocProfScope prof(MVOC_FAM_PNP, s,
-                     ntens * (elems * 2.0 * chunks + 2.0 * on * d->nobj * d->frames * d->height * d->width) +
-                         8.0 * nvar * d->nobj * d->frames);
-  const dim3 grid((unsigned)nblk, ntens);
-  const unsigned act = active;
-  const int* pl = (const int*)place;
-  switch (d->nobj) {
-    case 1: hipLaunchKernelGGL(pnp_tokens_placed_variants_kernel<1>, grid, dim3(256), 0, s, a, (int)nvar, act, pl); break;
-    case 2: hipLaunchKernelGGL(pnp_tokens_placed_variants_kernel<2>, grid, dim3(256), 0, s, a, (int)nvar, act, pl); break;
-    case 3: hipLaunchKernelGGL(pnp_tokens_placed_variants_kernel<3>, grid, dim3(256), 0, s, a, (int)nvar, act, pl); break;
-    default: hipLaunchKernelGGL(pnp_tokens_placed_variants_kernel<4>, grid, dim3(256), 0, s, a, (int)nvar, act, pl); break;
-  }
-  return mvoc_check_launch("pnp_tokens_placed_variants_kernel");
-}
-
-extern "C" int mvoc_pnp_blend_scatter_nchw_placed_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
-                                                           int32_t nvar, uint32_t active, const int32_t* place, void* stream) {
-  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_nchw_placed_variants")) return rc;
-  PnpArgs a;
-  double chunks = 0;
-  int on = 0;
-  if (int rc = fill_placed_variants(d, nsrc, obj_chunk, nvar, active, place, a, chunks, on)) return rc;
-  const long hw = (long)d->height * d->width;
-  const bool vec = hw % 8 == 0;
-  a.total = (long)d->frames * d->channels * (vec ? hw / 8 : hw);
-  const long nblk = (a.total + 255) / 256;
-  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "pnp nchw: grid too large");
-  const int ntens = d->x2 ? 2 : 1;
-  hipStream_t s = (hipStream_t)stream;
-  const double elems = (double)d->frames * hw * d->channels;
-  MvocProfScope prof(MVOC_FAM_PNP, s,
-                     ntens * (elems * 2.0 * chunks + 2.0 * on * d->nobj * d->frames * hw) + 8.0 * nvar * d->nobj * d->frames);
-  const dim3 grid((unsigned)nblk, ntens);
-  const int* pl = (const int*)place;
-  switch (d->nobj) {
-    case 1: launch_nchw_placed_variants_n<1>(vec, grid, s, a, nvar, active, pl); break;
-    case 2: launch_nchw_placed_variants_n<2>(vec, grid, s, a, nvar, active, pl); break;
-    case 3: launch_nchw_placed_variants_n<3>(vec, grid, s, a, nvar, active, pl); break;
-    default: launch_nchw_placed_variants_n<4>(vec, grid, s, a, nvar, active, pl); break;
-  }
-  return mvoc_check_launch("pnp_nchw_placed_variants_kernel");
-}
-
-namespace {
-
 // _resampled: the _placed contract with the table of per-axis index maps in place of the offset table
 int fill_resampled(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar, uint32_t active, const void* maps,
                    PnpArgs& a, double& chunks) {
@@ -1290,42 +774,136 @@ int fill_resampled(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chun
   return fill_variants_sel(d, nsrc, obj_chunk, nvar, active, a, chunks);
 }
 
-template <int NOBJ>
-void launch_nchw_resampled_n(bool vec, dim3 grid, hipStream_t s, const PnpArgs& a, int nvar, unsigned active, const int* maps) {
-  if (vec)
-    hipLaunchKernelGGL((pnp_nchw_resampled_kernel<8, NOBJ>), grid, dim3(256), 0, s, a, nvar, active, maps);
-  else
-    hipLaunchKernelGGL((pnp_nchw_resampled_kernel<1, NOBJ>), grid, dim3(256), 0, s, a, nvar, active, maps);
+}  // namespace
+
+extern "C" int mvoc_pnp_blend_scatter_tokens_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
+                                                      int32_t nvar, void* stream) {
+  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_tokens_variants")) return rc;
+  PnpArgs a;
+  Launch l;
+  double chunks = 0;
+  if (int rc = fill_variants(d, nsrc, obj_chunk, nvar, a, chunks)) return rc;
+  if (int rc = prepare_tokens(d, a, stream, l)) return rc;
+  MvocProfScope prof(MVOC_FAM_PNP, l.s, blend_bytes(l, d->nobj, chunks));
+  dispatch(d->nobj, l.vec, [&](auto n, auto) { launch(pnp_tokens_variants_kernel<n.value>, l, a, (int)nvar); });
+  return mvoc_check_launch("pnp_tokens_variants_kernel");
 }
 
-}  // namespace
+extern "C" int mvoc_pnp_blend_scatter_nchw_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
+                                                    int32_t nvar, void* stream) {
+  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_nchw_variants")) return rc;
+  PnpArgs a;
+  Launch l;
+  double chunks = 0;
+  if (int rc = fill_variants(d, nsrc, obj_chunk, nvar, a, chunks)) return rc;
+  if (int rc = prepare_nchw(d, a, stream, l)) return rc;
+  MvocProfScope prof(MVOC_FAM_PNP, l.s, blend_bytes(l, d->nobj, chunks));
+  dispatch(d->nobj, l.vec, [&](auto n, auto v) { launch(pnp_nchw_variants_kernel<v.value, n.value>, l, a, (int)nvar); });
+  return mvoc_check_launch("pnp_nchw_variants_kernel");
+}
+
+extern "C" int mvoc_pnp_blend_scatter_tokens_variants_sel(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
+                                                          int32_t nvar, uint32_t active, void* stream) {
+  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_tokens_variants_sel")) return rc;
+  PnpArgs a;
+  Launch l;
+  double chunks = 0;
+  if (int rc = fill_variants_sel(d, nsrc, obj_chunk, nvar, active, a, chunks)) return rc;
+  if (int rc = prepare_tokens(d, a, stream, l)) return rc;
+  MvocProfScope prof(MVOC_FAM_PNP, l.s, blend_bytes(l, d->nobj, chunks));
+  dispatch(d->nobj, l.vec, [&](auto n, auto) { launch(pnp_tokens_variants_sel_kernel<n.value>, l, a, (int)nvar, (unsigned)active); });
+  return mvoc_check_launch("pnp_tokens_variants_sel_kernel");
+}
+
+extern "C" int mvoc_pnp_blend_scatter_nchw_variants_sel(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
+                                                        int32_t nvar, uint32_t active, void* stream) {
+  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_nchw_variants_sel")) return rc;
+  PnpArgs a;
+  Launch l;
+  double chunks = 0;
+  if (int rc = fill_variants_sel(d, nsrc, obj_chunk, nvar, active, a, chunks)) return rc;
+  if (int rc = prepare_nchw(d, a, stream, l)) return rc;
+  MvocProfScope prof(MVOC_FAM_PNP, l.s, blend_bytes(l, d->nobj, chunks));
+  dispatch(d->nobj, l.vec,
+           [&](auto n, auto v) { launch(pnp_nchw_variants_sel_kernel<v.value, n.value>, l, a, (int)nvar, (unsigned)active); });
+  return mvoc_check_launch("pnp_nchw_variants_sel_kernel");
+}
+
+extern "C" int mvoc_pnp_blend_scatter_tokens_placed(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
+                                                    uint32_t active, const int32_t* place, void* stream) {
+  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_tokens_placed")) return rc;
+  PnpArgs a;
+  Launch l;
+  double chunks = 0;
+  if (int rc = fill_placed(d, nsrc, obj_chunk, nvar, active, place, a, chunks)) return rc;
+  if (int rc = prepare_tokens(d, a, stream, l)) return rc;
+  MvocProfScope prof(MVOC_FAM_PNP, l.s, blend_bytes(l, d->nobj, chunks));
+  dispatch(d->nobj, l.vec, [&](auto n, auto) {
+    launch(pnp_tokens_placed_kernel<n.value>, l, a, (int)nvar, (unsigned)active, (const int*)place);
+  });
+  return mvoc_check_launch("pnp_tokens_placed_kernel");
+}
+
+extern "C" int mvoc_pnp_blend_scatter_nchw_placed(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
+                                                  uint32_t active, const int32_t* place, void* stream) {
+  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_nchw_placed")) return rc;
+  PnpArgs a;
+  Launch l;
+  double chunks = 0;
+  if (int rc = fill_placed(d, nsrc, obj_chunk, nvar, active, place, a, chunks)) return rc;
+  if (int rc = prepare_nchw(d, a, stream, l)) return rc;
+  MvocProfScope prof(MVOC_FAM_PNP, l.s, blend_bytes(l, d->nobj, chunks));
+  dispatch(d->nobj, l.vec, [&](auto n, auto v) {
+    launch(pnp_nchw_placed_kernel<v.value, n.value>, l, a, (int)nvar, (unsigned)active, (const int*)place);
+  });
+  return mvoc_check_launch("pnp_nchw_placed_kernel");
+}
+
+extern "C" int mvoc_pnp_blend_scatter_tokens_placed_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
+                                                             int32_t nvar, uint32_t active, const int32_t* place, void* stream) {
+  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_tokens_placed_variants")) return rc;
+  PnpArgs a;
+  Launch l;
+  double chunks = 0;
+  int on = 0;
+  if (int rc = fill_placed_variants(d, nsrc, obj_chunk, nvar, active, place, a, chunks, on)) return rc;
+  if (int rc = prepare_tokens(d, a, stream, l)) return rc;
+  MvocProfScope prof(MVOC_FAM_PNP, l.s, blend_bytes(l, d->nobj, chunks, on, 8.0 * nvar * d->nobj * d->frames));
+  dispatch(d->nobj, l.vec, [&](auto n, auto) {
+    launch(pnp_tokens_placed_variants_kernel<n.value>, l, a, (int)nvar, (unsigned)active, (const int*)place);
+  });
+  return mvoc_check_launch("pnp_tokens_placed_variants_kernel");
+}
+
+extern "C" int mvoc_pnp_blend_scatter_nchw_placed_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
+                                                           int32_t nvar, uint32_t active, const int32_t* place, void* stream) {
+  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_nchw_placed_variants")) return rc;
+  PnpArgs a;
+  Launch l;
+  double chunks = 0;
+  int on = 0;
+  if (int rc = fill_placed_variants(d, nsrc, obj_chunk, nvar, active, place, a, chunks, on)) return rc;
+  if (int rc = prepare_nchw(d, a, stream, l)) return rc;
+  MvocProfScope prof(MVOC_FAM_PNP, l.s, blend_bytes(l, d->nobj, chunks, on, 8.0 * nvar * d->nobj * d->frames));
+  dispatch(d->nobj, l.vec, [&](auto n, auto v) {
+    launch(pnp_nchw_placed_variants_kernel<v.value, n.value>, l, a, (int)nvar, (unsigned)active, (const int*)place);
+  });
+  return mvoc_check_launch("pnp_nchw_placed_variants_kernel");
+}
 
 extern "C" int mvoc_pnp_blend_scatter_tokens_resampled(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
                                                        uint32_t active, const int32_t* maps, void* stream) {
   if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_tokens_resampled")) return rc;
   PnpArgs a;
+  Launch l;
   double chunks = 0;
   if (int rc = fill_resampled(d, nsrc, obj_chunk, nvar, active, maps, a, chunks)) return rc;
-  MVOC_REQUIRE(d->channels % 8 == 0 && d->chunk_stride % 8 == 0 && d->f_stride % 8 == 0 && d->p_stride % 8 == 0, -2,
-               "pnp tokens: channels/strides must be multiples of 8");
-  a.total = (long)d->frames * d->height * d->width * (d->channels / 8);
-  const long nblk = (a.total + 255) / 256;
-  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "pnp tokens: grid too large");
-  const int ntens = d->x2 ? 2 : 1;
-  hipStream_t s = (hipStream_t)stream;
-  const double elems = (double)d->frames * d->height * d->width * d->channels;
-  MvocProfScope prof(MVOC_FAM_PNP, s,
-                     ntens * (elems * 2.0 * chunks + 2.0 * d->nobj * d->frames * d->height * d->width) +
-                         4.0 * d->nobj * d->frames * ((double)d->height + d->width));
-  const dim3 grid((unsigned)nblk, ntens);
-  const unsigned act = active;
-  const int* mp = (const int*)maps;
-  switch (d->nobj) {
-    case 1: hipLaunchKernelGGL(pnp_tokens_resampled_kernel<1>, grid, dim3(256), 0, s, a, (int)nvar, act, mp); break;
-    case 2: hipLaunchKernelGGL(pnp_tokens_resampled_kernel<2>, grid, dim3(256), 0, s, a, (int)nvar, act, mp); break;
-    case 3: hipLaunchKernelGGL(pnp_tokens_resampled_kernel<3>, grid, dim3(256), 0, s, a, (int)nvar, act, mp); break;
-    default: hipLaunchKernelGGL(pnp_tokens_resampled_kernel<4>, grid, dim3(256), 0, s, a, (int)nvar, act, mp); break;
-  }
+  if (int rc = prepare_tokens(d, a, stream, l)) return rc;
+  MvocProfScope prof(MVOC_FAM_PNP, l.s,
+                     blend_bytes(l, d->nobj, chunks, 1.0, 4.0 * d->nobj * d->frames * ((double)d->height + d->width)));
+  dispatch(d->nobj, l.vec, [&](auto n, auto) {
+    launch(pnp_tokens_resampled_kernel<n.value>, l, a, (int)nvar, (unsigned)active, (const int*)maps);
+  });
   return mvoc_check_launch("pnp_tokens_resampled_kernel");
 }
 
@@ -1333,27 +911,15 @@ extern "C" int mvoc_pnp_blend_scatter_nchw_resampled(const mvoc_pnp_desc* d, int
                                                      uint32_t active, const int32_t* maps, void* stream) {
   if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_nchw_resampled")) return rc;
   PnpArgs a;
+  Launch l;
   double chunks = 0;
   if (int rc = fill_resampled(d, nsrc, obj_chunk, nvar, active, maps, a, chunks)) return rc;
-  const long hw = (long)d->height * d->width;
-  const bool vec = hw % 8 == 0;
-  a.total = (long)d->frames * d->channels * (vec ? hw / 8 : hw);
-  const long nblk = (a.total + 255) / 256;
-  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "pnp nchw: grid too large");
-  const int ntens = d->x2 ? 2 : 1;
-  hipStream_t s = (hipStream_t)stream;
-  const double elems = (double)d->frames * hw * d->channels;
-  MvocProfScope prof(MVOC_FAM_PNP, s,
-                     ntens * (elems * 2.0 * chunks + 2.0 * d->nobj * d->frames * hw) +
-                         4.0 * d->nobj * d->frames * ((double)d->height + d->width));
-  const dim3 grid((unsigned)nblk, ntens);
-  const int* mp = (const int*)maps;
-  switch (d->nobj) {
-    case 1: launch_nchw_resampled_n<1>(vec, grid, s, a, nvar, active, mp); break;
-    case 2: launch_nchw_resampled_n<2>(vec, grid, s, a, nvar, active, mp); break;
-    case 3: launch_nchw_resampled_n<3>(vec, grid, s, a, nvar, active, mp); break;
-    default: launch_nchw_resampled_n<4>(vec, grid, s, a, nvar, active, mp); break;
-  }
+  if (int rc = prepare_nchw(d, a, stream, l)) return rc;
+  MvocProfScope prof(MVOC_FAM_PNP, l.s,
+                     blend_bytes(l, d->nobj, chunks, 1.0, 4.0 * d->nobj * d->frames * ((double)d->height + d->width)));
+  dispatch(d->nobj, l.vec, [&](auto n, auto v) {
+    launch(pnp_nchw_resampled_kernel<v.value, n.value>, l, a, (int)nvar, (unsigned)active, (const int*)maps);
+  });
   return mvoc_check_launch("pnp_nchw_resampled_kernel");
 }
 

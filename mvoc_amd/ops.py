@@ -549,6 +549,34 @@ def _active_mask(active, nvar, what):
     return None if active == (1 << nvar) - 1 else active
 
 
+def _pnp_blend(layout, d, x, x2, masks, need, ndst, src_map, nvar, active, place, resample):
+    """pick the library entry mvoc_pnp_blend_scatter_<layout><suffix> for the arguments of ``pnp_blend_<layout>`` and call it on
+    the descriptor ``d``; ``need(nchunk)``: elements a tensor must hold from its first for a batch of nchunk chunks"""
+    what = f"pnp_blend_{layout}"
+
+    def call(suffix, *args):
+        name = f"pnp_blend_scatter_{layout}{suffix}"
+        check(getattr(lib, "mvoc_" + name)(C.byref(d), *args, _stream()), name)
+
+    if masks.dim() == 5 and (place is None or place.dim() != 4):
+        raise RuntimeError(f"{what}: a [K, nobj, F, mh, mw] mask stack needs place= as an int32 [K, nobj, F, 2] table")
+    if nvar == 1 and place is None and resample is None:
+        return call("") if src_map is None else call("_mapped", *_src_map_args(src_map, d.nobj))
+    nsrc, chunks = _variant_map(src_map, d.nobj)
+    _check_variants(x, x2, nvar, need(nsrc + (int(ndst) or 2) * int(nvar)), what)
+    if resample is not None:
+        _check_resample(resample, d.nobj, d.frames, d.height, d.width, what)
+        return call("_resampled", nsrc, chunks, int(nvar), _all_or(active, nvar), resample.data_ptr())
+    if _check_place_variants(place, masks, nvar, d.nobj, d.frames, what):
+        return call("_placed_variants", nsrc, chunks, int(nvar), _all_or(active, nvar), place.data_ptr())
+    if place is not None:
+        _check_place(place, d.nobj, d.frames, what)
+        return call("_placed", nsrc, chunks, int(nvar), _all_or(active, nvar), place.data_ptr())
+    if active is not None:
+        return call("_variants_sel", nsrc, chunks, int(nvar), active)
+    return call("_variants", nsrc, chunks, int(nvar))
+
+
 def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride, f_stride, p_stride, x2=None,
                      base_chunk0=False, ndst=2, src_map=None, nvar=1, active=None, place=None, no_background=False, resample=None):
     """In-place masked blend + scatter on channel-contiguous data (see include/mvoc_hip.h).  ``ndst``: trailing
@@ -577,39 +605,9 @@ def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride,
         last = (d.nobj + (int(ndst) or 2) - 1) * chunk_stride
         _check_variants(x, x2, 1, last + (frames - 1) * f_stride + (height * width - 1) * p_stride + channels, "pnp_blend_tokens")
         d.base_chunk0 = -1  # (include/mvoc_hip.h: no background chunk, the base is the last chunk)
-    if masks.dim() == 5 and (place is None or place.dim() != 4):
-        raise RuntimeError("pnp_blend_tokens: a [K, nobj, F, mh, mw] mask stack needs place= as an int32 [K, nobj, F, 2] table")
-    if nvar != 1 or place is not None or resample is not None:
-        nsrc, chunks = _variant_map(src_map, d.nobj)
-        last = (nsrc + (int(ndst) or 2) * int(nvar) - 1) * chunk_stride
-        _check_variants(x, x2, nvar, last + (frames - 1) * f_stride + (height * width - 1) * p_stride + channels,
-                        "pnp_blend_tokens")
-        if resample is not None:
-            _check_resample(resample, d.nobj, frames, height, width, "pnp_blend_tokens")
-            check(lib.mvoc_pnp_blend_scatter_tokens_resampled(C.byref(d), nsrc, chunks, int(nvar), _all_or(active, nvar),
-                                                              resample.data_ptr(), _stream()), "pnp_blend_scatter_tokens_resampled")
-            return x
-        if _check_place_variants(place, masks, nvar, d.nobj, frames, "pnp_blend_tokens"):
-            check(lib.mvoc_pnp_blend_scatter_tokens_placed_variants(C.byref(d), nsrc, chunks, int(nvar), _all_or(active, nvar),
-                                                                    place.data_ptr(), _stream()),
-                  "pnp_blend_scatter_tokens_placed_variants")
-            return x
-        if place is not None:
-            _check_place(place, d.nobj, frames, "pnp_blend_tokens")
-            check(lib.mvoc_pnp_blend_scatter_tokens_placed(C.byref(d), nsrc, chunks, int(nvar), _all_or(active, nvar),
-                                                           place.data_ptr(), _stream()), "pnp_blend_scatter_tokens_placed")
-            return x
-        if active is not None:
-            check(lib.mvoc_pnp_blend_scatter_tokens_variants_sel(C.byref(d), nsrc, chunks, int(nvar), active, _stream()),
-                  "pnp_blend_scatter_tokens_variants_sel")
-            return x
-        check(lib.mvoc_pnp_blend_scatter_tokens_variants(C.byref(d), nsrc, chunks, int(nvar), _stream()),
-              "pnp_blend_scatter_tokens_variants")
-    elif src_map is None:
-        check(lib.mvoc_pnp_blend_scatter_tokens(C.byref(d), _stream()), "pnp_blend_scatter_tokens")
-    else:
-        nsrc, chunks = _src_map_args(src_map, d.nobj)
-        check(lib.mvoc_pnp_blend_scatter_tokens_mapped(C.byref(d), nsrc, chunks, _stream()), "pnp_blend_scatter_tokens_mapped")
+    reach = (frames - 1) * f_stride + (height * width - 1) * p_stride + channels  # of the last chunk's last element
+    _pnp_blend("tokens", d, x, x2, masks, lambda nchunk: (nchunk - 1) * chunk_stride + reach, ndst, src_map, nvar, active, place,
+               resample)
     return x
 
 
@@ -624,37 +622,7 @@ def pnp_blend_nchw(x, masks, *, frames, x2=None, base_chunk0=True, ndst=2, src_m
         _refuse_resample_mix(place, masks, False, "pnp_blend_nchw")
     d = _pnp_desc(x, x2, masks, 0, 0, 0, frames, x.shape[2], x.shape[3], x.shape[1], base_chunk0, ndst)
     active = _active_mask(active, nvar, "pnp_blend_nchw")
-    if masks.dim() == 5 and (place is None or place.dim() != 4):
-        raise RuntimeError("pnp_blend_nchw: a [K, nobj, F, mh, mw] mask stack needs place= as an int32 [K, nobj, F, 2] table")
-    if nvar != 1 or place is not None or resample is not None:
-        nsrc, chunks = _variant_map(src_map, d.nobj)
-        _check_variants(x, x2, nvar, (nsrc + (int(ndst) or 2) * int(nvar)) * frames * x[0].numel(), "pnp_blend_nchw")
-        if resample is not None:
-            _check_resample(resample, d.nobj, frames, x.shape[2], x.shape[3], "pnp_blend_nchw")
-            check(lib.mvoc_pnp_blend_scatter_nchw_resampled(C.byref(d), nsrc, chunks, int(nvar), _all_or(active, nvar),
-                                                            resample.data_ptr(), _stream()), "pnp_blend_scatter_nchw_resampled")
-            return x
-        if _check_place_variants(place, masks, nvar, d.nobj, frames, "pnp_blend_nchw"):
-            check(lib.mvoc_pnp_blend_scatter_nchw_placed_variants(C.byref(d), nsrc, chunks, int(nvar), _all_or(active, nvar),
-                                                                  place.data_ptr(), _stream()),
-                  "pnp_blend_scatter_nchw_placed_variants")
-            return x
-        if place is not None:
-            _check_place(place, d.nobj, frames, "pnp_blend_nchw")
-            check(lib.mvoc_pnp_blend_scatter_nchw_placed(C.byref(d), nsrc, chunks, int(nvar), _all_or(active, nvar),
-                                                         place.data_ptr(), _stream()), "pnp_blend_scatter_nchw_placed")
-            return x
-        if active is not None:
-            check(lib.mvoc_pnp_blend_scatter_nchw_variants_sel(C.byref(d), nsrc, chunks, int(nvar), active, _stream()),
-                  "pnp_blend_scatter_nchw_variants_sel")
-            return x
-        check(lib.mvoc_pnp_blend_scatter_nchw_variants(C.byref(d), nsrc, chunks, int(nvar), _stream()),
-              "pnp_blend_scatter_nchw_variants")
-    elif src_map is None:
-        check(lib.mvoc_pnp_blend_scatter_nchw(C.byref(d), _stream()), "pnp_blend_scatter_nchw")
-    else:
-        nsrc, chunks = _src_map_args(src_map, d.nobj)
-        check(lib.mvoc_pnp_blend_scatter_nchw_mapped(C.byref(d), nsrc, chunks, _stream()), "pnp_blend_scatter_nchw_mapped")
+    _pnp_blend("nchw", d, x, x2, masks, lambda nchunk: nchunk * frames * x[0].numel(), ndst, src_map, nvar, active, place, resample)
     return x
 
 
