@@ -192,7 +192,15 @@ int mvoc_temporal_attn_f16(const mvoc_tattn_desc* d, void* stream);
  *      piece k/16    : its first 128 bytes are the tile's 32 constants c[32 tile + i] as fp32 (bias, or beta @ W^T + bias)
  * normalize != 0 folds a LayerNorm in front (rows normalised in registers; W must be gamma-scaled, c = beta @ W^T + bias).
  * act as for mvoc_gemm_f16 (GEGLU: weight rows in (value, gate) blocks of 32, n/2 outputs, no residual).  x is [m][k]
- * contiguous; out / resid rows 16-byte addressable per 8 channels; n_store may only trim the last 32-channel tile. */
+ * contiguous; out / resid rows 16-byte addressable per 8 channels; n_store may only trim the last 32-channel tile.
+ * Extents (enforced by tests/test_xs_contract_gpu.py on allocations whose undescribed elements are NaN; cols = n_store, or
+ * n (GEGLU: n / 2) where n_store is 0):
+ *   - only the elements x[m][k], the wp stream(s) ((m / wp_set_rows, or 1) x n/32 tiles x (k/16 + 1) KB), of each tile's
+ *     constants piece its first 128 bytes, and resid[m][cols] at pitch ldr influence a result: the other 896 bytes of a
+ *     constants piece, the residual's columns >= cols and the gaps between its rows, and whatever lies around x, wp and resid
+ *     never do, whatever they hold;
+ *   - no byte of out outside [m][cols] at pitch ldo is written;
+ *   - x and wp must be 16-byte aligned (both are read in 16-byte pieces); a misaligned pointer is refused with -2. */
 typedef struct mvoc_xs_desc {
   const void* x;
   const void* wp;

@@ -387,6 +387,8 @@ extern "C" int mvoc_xs_linear_f16(const mvoc_xs_desc* d, void* stream) {
   MVOC_REQUIRE(ns % 8 == 0 && d->ldo % 8 == 0 && ((uintptr_t)d->out & 15) == 0 &&
                    (d->resid == nullptr || (d->ldr % 8 == 0 && ((uintptr_t)d->resid & 15) == 0)),
                -2, "xs_linear: outputs / residual must be 16-byte addressable per 8 channels");
+  MVOC_REQUIRE(((uintptr_t)d->x & 15) == 0 && ((uintptr_t)d->wp & 15) == 0, -2,
+               "xs_linear: x / wp must be 16-byte addressable (both are read in 16-byte pieces)");
   XsArgs a;
   a.x = (const half_t*)d->x; a.wp = (const half_t*)d->wp;
   a.resid = (const half_t*)d->resid; a.out = (half_t*)d->out;
