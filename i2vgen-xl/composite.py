@@ -15,7 +15,8 @@ A variant's ``placement: [[dx, dy], ...]`` (the format of ``obj_offset``) places
 (``variant_placement_kwargs``); a variant without the key takes the entry's ``obj_offset``, or none.
 An entry's ``obj_transform: [{offset, scale, flip, anchor}, ...]`` (one dict per object, every key optional) scales, mirrors and
 places the objects at composition time (``transform_kwargs``; shared by the entry's variants, not with ``obj_offset`` or a
-variant's ``placement``).
+variant's ``placement``).  A variant's ``transform: [{...}, ...]`` (the format of ``obj_transform``) transforms the objects for
+that variant alone; a variant without the key takes the entry's ``obj_transform``, or none.
 """
 import argparse
 import json
@@ -86,9 +87,10 @@ def output_suffix(config):
 # what one variant of an entry may override; every other key is shared by the variants of a call (sources, masks, the entry's
 # schedules, fusion settings: the source chunks are computed once for all of them).  "pnp" is a dict of injection thresholds
 # of the variant's own (any of PNP_KEYS) -- the flat threshold keys stay the entry's.  "placement" is the variant's
-# own object placement in the format of the entry's ``obj_offset`` -- ``obj_offset`` itself stays the entry's
+# own object placement in the format of the entry's ``obj_offset`` -- ``obj_offset`` itself stays the entry's;
+# "transform" the variant's own scale / mirror / offset in the format of the entry's ``obj_transform``
 VARIANT_KEYS = ("editing_prompt", "editing_negative_prompt", "seed", "cfg", "edited_first_frame_path",
-                "edited_contorl_frame_path_main", "pnp", "placement")
+                "edited_contorl_frame_path_main", "pnp", "placement", "transform")
 PNP_KEYS = ("pnp_f_t", "pnp_spatial_attn_t", "pnp_temp_attn_t")
 MAX_VARIANTS = 8
 
@@ -163,18 +165,30 @@ def transform_kwargs(config, variants=None):
     with the placements of ``variant_placement_kwargs``: none of the keys -> {} (exactly today's call); ``obj_transform`` alone
     -> ``obj_transforms`` as plain dicts and lists (the call checks and normalises them; shared by the entry's variants: not one
     of ``VARIANT_KEYS``); together with ``obj_offset`` or any variant's ``placement`` it is an error -- a transform carries its
-    own offset.  ``obj_width_height`` stays ignored, as in the reference."""
+    own offset.  ``obj_width_height`` stays ignored, as in the reference.
+    A variant's ``transform`` (the format of ``obj_transform``) transforms the objects for that variant alone:
+    ``variant_obj_transforms`` = one item per variant -- the variant's ``transform``, or the entry's ``obj_transform`` (None
+    without one) for a variant that does not set the key; not with the entry's ``obj_offset`` or any variant's ``placement``."""
+    def plain(v):
+        if hasattr(v, "keys"):
+            return {str(k): plain(v[k]) for k in v.keys()}
+        return [plain(x) for x in v] if hasattr(v, "__iter__") and not isinstance(v, (str, bytes)) else v
+
+    if variants is not None and any("transform" in c and c.transform is not None for c in variants):
+        if "obj_offset" in config and config.obj_offset is not None:
+            raise ValueError("a variant sets 'transform' and the entry sets obj_offset: put the offset into the transform ('offset')")
+        if any("placement" in c and c.placement is not None for c in variants):
+            raise ValueError("a variant sets 'transform' and a variant sets 'placement': put the offset into the transform "
+                             "('offset')")
+        shared = plain(config.obj_transform) if "obj_transform" in config and config.obj_transform is not None else None
+        return {"variant_obj_transforms": [plain(c.transform) if "transform" in c and c.transform is not None else shared
+                                           for c in variants]}
     if "obj_transform" not in config or config.obj_transform is None:
         return variant_placement_kwargs(config, variants)
     if "obj_offset" in config and config.obj_offset is not None:
         raise ValueError("obj_transform and obj_offset are both set: put the offset into the transform ('offset')")
     if variants is not None and any("placement" in c and c.placement is not None for c in variants):
         raise ValueError("obj_transform is set and a variant sets 'placement': one transform serves all variants of an entry")
-
-    def plain(v):
-        if hasattr(v, "keys"):
-            return {str(k): plain(v[k]) for k in v.keys()}
-        return [plain(x) for x in v] if hasattr(v, "__iter__") and not isinstance(v, (str, bytes)) else v
     return {"obj_transforms": plain(config.obj_transform)}
 
 

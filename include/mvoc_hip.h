@@ -424,6 +424,22 @@ int mvoc_pnp_blend_scatter_tokens_resampled(const mvoc_pnp_desc* d, int32_t nsrc
                                             uint32_t active, const int32_t* maps, void* stream);
 int mvoc_pnp_blend_scatter_nchw_resampled(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
                                           uint32_t active, const int32_t* maps, void* stream);
+/* Per-variant transforms: the _resampled entries with a map table and masks PER VARIANT, in the shape of
+ * _placed_variants.  `maps` is a DEVICE table of int32 [nvar][nobj][frames][height + width] (ymap, then xmap) for this call's
+ * height x width; variant k reads object j of frame f at (ymap[py], xmap[px]) taken from row (k * nobj + j) * frames + f (the
+ * row offset is formed in 64 bits).  d->masks points at [nvar][nobj][frames][mask_h][mask_w]: variant k's masks in ITS
+ * destination coordinates.  Absent objects (every int32 entry is safe), the three fp16-rounded ops per object, object order,
+ * ndst, base_chunk0, the source map and `active` are those of _resampled; the chunks of a variant whose bit is clear are neither
+ * read nor written.  Variant k's destination rows are bit-identical to the _resampled entry with nvar = 1 on that variant's own
+ * [sources.., (u_k,) c_k] batch with table k and masks k; nvar = 1 is the _resampled entry, translation-only tables are the
+ * _placed_variants entry with the matching offsets.  Bytes counted per launch (MvocProfScope): the chunk and mask terms of
+ * _placed_variants + 4 * nvar*nobj*frames*(height + width) for the table.
+ * Requires a non-NULL table, 1 <= nvar <= 8, 1 <= active < (1u << nvar), a valid map and base_chunk0 != -1 (else -1 and an error
+ * text, nothing written). */
+int mvoc_pnp_blend_scatter_tokens_resampled_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
+                                                     uint32_t active, const int32_t* maps, void* stream);
+int mvoc_pnp_blend_scatter_nchw_resampled_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
+                                                   uint32_t active, const int32_t* maps, void* stream);
 /* Zero-filled per-frame gather of contiguous fp16 planes [nplane][frames][h][w] (src != dst):
  *     dst[pl][f][y][x] = src[pl][f][ymap_f[y]][xmap_f[x]], or 0 where either index lies outside the plane
  * `maps`: DEVICE int32 [frames][h + w], ymap_f (h entries) and then xmap_f (w entries), shared by the nplane planes (the planes

@@ -558,12 +558,16 @@ def _pnp_blend(layout, d, x, x2, masks, need, ndst, src_map, nvar, active, place
         name = f"pnp_blend_scatter_{layout}{suffix}"
         check(getattr(lib, "mvoc_" + name)(C.byref(d), *args, _stream()), name)
 
-    if masks.dim() == 5 and (place is None or place.dim() != 4):
+    per_variant_maps = resample is not None and _check_resample_variants(resample, masks, nvar, d.nobj, d.frames, d.height,
+                                                                         d.width, what)
+    if masks.dim() == 5 and not per_variant_maps and (place is None or place.dim() != 4):
         raise RuntimeError(f"{what}: a [K, nobj, F, mh, mw] mask stack needs place= as an int32 [K, nobj, F, 2] table")
     if nvar == 1 and place is None and resample is None:
         return call("") if src_map is None else call("_mapped", *_src_map_args(src_map, d.nobj))
     nsrc, chunks = _variant_map(src_map, d.nobj)
     _check_variants(x, x2, nvar, need(nsrc + (int(ndst) or 2) * int(nvar)), what)
+    if per_variant_maps:
+        return call("_resampled_variants", nsrc, chunks, int(nvar), _all_or(active, nvar), resample.data_ptr())
     if resample is not None:
         _check_resample(resample, d.nobj, d.frames, d.height, d.width, what)
         return call("_resampled", nsrc, chunks, int(nvar), _all_or(active, nvar), resample.data_ptr())
@@ -591,9 +595,11 @@ def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride,
     there).
     ``resample``: the table of ``resample_table`` for this height x width: every object is read at the pixel its
     per-axis maps name (scale, mirror and translation, nearest), ``masks`` are in destination coordinates -- the ``_resampled``
-    entry, whatever ``nvar`` / ``src_map`` / ``active`` are.  Not with ``place``, not with a per-variant mask stack."""
+    entry, whatever ``nvar`` / ``src_map`` / ``active`` are.  Not with ``place``, not with a per-variant mask stack.
+    A 4-D ``resample`` (``resample_table_variants``) with a [K, nobj, F, mh, mw] mask stack: a transform and masks
+    per variant -- the ``_resampled_variants`` entry."""
     if resample is not None:
-        _refuse_resample_mix(place, masks, no_background, "pnp_blend_tokens")
+        _refuse_resample_mix(place, masks, no_background, "pnp_blend_tokens", resample)
     d = _pnp_desc(x, x2, masks, chunk_stride, f_stride, p_stride, frames, height, width, channels, base_chunk0, ndst)
     active = _active_mask(active, nvar, "pnp_blend_tokens")
     if no_background:
@@ -619,7 +625,7 @@ def pnp_blend_nchw(x, masks, *, frames, x2=None, base_chunk0=True, ndst=2, src_m
     if x.dim() != 4 or not x.is_contiguous():
         raise RuntimeError("pnp_blend_nchw: x must be contiguous [N, C, H, W]")
     if resample is not None:
-        _refuse_resample_mix(place, masks, False, "pnp_blend_nchw")
+        _refuse_resample_mix(place, masks, False, "pnp_blend_nchw", resample)
     d = _pnp_desc(x, x2, masks, 0, 0, 0, frames, x.shape[2], x.shape[3], x.shape[1], base_chunk0, ndst)
     active = _active_mask(active, nvar, "pnp_blend_nchw")
     _pnp_blend("nchw", d, x, x2, masks, lambda nchunk: nchunk * frames * x[0].numel(), ndst, src_map, nvar, active, place, resample)
@@ -760,10 +766,43 @@ def resample_table(transform, height, width, mask_h, mask_w, device):
     return torch.tensor(transform_maps(transform, height, width, mask_h, mask_w), dtype=torch.int32).to(device).contiguous()
 
 
-def _refuse_resample_mix(place, masks, no_background, what):
+def resample_table_variants(variant_transforms, height, width, mask_h, mask_w, device):
+    """the device table the ``_resampled_variants`` blend entries read: int32 [K, nobj, F, height + width], row k
+    = ``resample_table`` of ``variant_transforms[k]`` (the same rule, ``level_axis_map``)"""
+    if not variant_transforms:
+        raise RuntimeError("resample_table_variants: needs at least one variant's transform")
+    rows = []
+    for k, tr in enumerate(variant_transforms):
+        try:
+            rows.append(transform_maps(tr, height, width, mask_h, mask_w))
+        except RuntimeError as e:
+            raise RuntimeError(f"resample_table_variants: variant {k}: {e}") from None
+    shapes = {(len(r), len(r[0])) for r in rows}
+    if len(shapes) != 1:
+        raise RuntimeError(f"resample_table_variants: the variants' tables differ in shape (objects, frames): {sorted(shapes)}")
+    return torch.tensor(rows, dtype=torch.int32).to(device).contiguous()
+
+
+def _check_resample_variants(maps, masks, nvar, nobj, frames, height, width, what):
+    """True when ``maps`` / ``masks`` are the per-variant pair (4-D table + 5-D mask stack); a 3-D table is the
+    shared transform (False; ``_refuse_resample_mix`` has refused a stack next to it); a 4-D table without the stack is an error"""
+    if not torch.is_tensor(maps) or maps.dim() != 4:
+        return False
+    _chk(maps, "resample", torch.int32)
+    nvar = int(nvar)
+    if tuple(maps.shape) != (nvar, nobj, frames, height + width) or not maps.is_contiguous():
+        raise RuntimeError(f"{what}: resample must be a contiguous int32 [K = {nvar}, nobj = {nobj}, F = {frames}, H + W = "
+                           f"{height + width}] table with a [K, nobj, F, mh, mw] mask stack, got {tuple(maps.shape)}")
+    if masks.dim() != 5 or tuple(masks.shape[:3]) != (nvar, nobj, frames) or not masks.is_contiguous():
+        raise RuntimeError(f"{what}: a [K, nobj, F, H + W] resample table needs masks as a contiguous [K = {nvar}, nobj = {nobj}, "
+                           f"F = {frames}, mh, mw] stack, got {tuple(masks.shape)}")
+    return True
+
+
+def _refuse_resample_mix(place, masks, no_background, what, resample=None):
     if place is not None:
         raise RuntimeError(f"{what}: resample= and place= are both given: a translation is part of the resample table")
-    if masks.dim() == 5:
+    if masks.dim() == 5 and not (torch.is_tensor(resample) and resample.dim() == 4):
         raise RuntimeError(f"{what}: resample= does not take a [K, nobj, F, mh, mw] mask stack: one transform serves all variants")
     if no_background:
         raise RuntimeError(f"{what}: resample= with no_background: pass src_map=(nobj, range(nobj)) instead")

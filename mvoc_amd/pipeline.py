@@ -283,6 +283,23 @@ def normalize_obj_transforms(obj_transforms, n_obj, num_frames, lat_h, lat_w, fa
     Anything else is a ValueError that names the object."""
     if obj_transforms is None:
         return None, None
+    return _downgrade_obj_transforms(_full_obj_transforms(obj_transforms, n_obj, num_frames, lat_h, lat_w, factor), num_frames)
+
+
+def _downgrade_obj_transforms(out, num_frames):
+    """full transform tuples -> (placement or None, transform or None) as ``normalize_obj_transforms`` documents"""
+    zero = ((0, 0),) * num_frames
+    plain = [t[0] == t[1] and t[2] == t[3] and not t[4] and not t[5] for t in out]
+    if all(plain):
+        if all(t[8] == zero for t in out):
+            return None, None
+        return tuple(t[8] for t in out), None
+    return None, tuple(out)
+
+
+def _full_obj_transforms(obj_transforms, n_obj, num_frames, lat_h, lat_w, factor=8):
+    """the items of ``obj_transforms`` checked and normalised -> per object the full tuple (py, qy, px, qx, flip_y, flip_x, ay2,
+    ax2, ((dy, dx) per frame)), identity and translation-only objects included"""
     if not isinstance(obj_transforms, (list, tuple)):
         raise ValueError(f"obj_transforms: needs a list of {n_obj} dicts (one per object), got {obj_transforms!r}")
     items = list(obj_transforms)
@@ -331,12 +348,41 @@ def normalize_obj_transforms(obj_transforms, n_obj, num_frames, lat_h, lat_w, fa
                                  "(anchors sit on half latent pixels)")
             ax2, ay2 = 2 * anchor[0] // factor, 2 * anchor[1] // factor
         out.append((py, qy, px, qx, flip_y, flip_x, ay2, ax2, tuple(offs)))
-    plain = [t[0] == t[1] and t[2] == t[3] and not t[4] and not t[5] for t in out]
-    if all(plain):
-        if all(t[8] == zero for t in out):
-            return None, None
-        return tuple(t[8] for t in out), None
-    return None, tuple(out)
+    return tuple(out)
+
+
+def resolve_variant_obj_transforms(variant_obj_transforms, nvar, n_obj, num_frames, lat_h, lat_w, factor=8):
+    """``variant_obj_transforms`` of the sampling call: K = ``nvar`` items, each None or a value ``obj_transforms``
+    accepts, normalised per variant by ``normalize_obj_transforms``' rules -> (placement, variant_placements, transform,
+    variant_transforms), at most one of them not None, resolved in this order:
+      all None                    every variant at identity: exactly a call without the argument
+      placement or transform      all variants equal: exactly the shared ``obj_transforms`` call (``obj_offsets`` when it only
+                                  translates)
+      variant_placements          every variant at scale 1 without a flip: exactly the ``variant_obj_offsets`` call
+      variant_transforms          else: K full transform tuples, identity and translation-only variants included
+    Anything else is a ValueError that names the variant (and, from ``normalize_obj_transforms``, the object)."""
+    if variant_obj_transforms is None:
+        return None, None, None, None
+    if not isinstance(variant_obj_transforms, (list, tuple)):
+        raise ValueError(f"variant_obj_transforms: needs a list of {nvar} items (one per variant), got {variant_obj_transforms!r}")
+    items = list(variant_obj_transforms)
+    if len(items) != nvar:
+        raise ValueError(f"variant_obj_transforms: {len(items)} entries for {nvar} variants (one per variant)")
+    fulls = []
+    for k, item in enumerate(items):
+        try:
+            fulls.append(_full_obj_transforms([None] * n_obj if item is None else item, n_obj, num_frames, lat_h, lat_w, factor))
+        except ValueError as e:
+            raise ValueError(f"variant_obj_transforms: variant {k}: {e}") from None
+    downs = [_downgrade_obj_transforms(f, num_frames) for f in fulls]
+    if all(d == (None, None) for d in downs):
+        return None, None, None, None
+    if all(f == fulls[0] for f in fulls):
+        return downs[0][0], None, downs[0][1], None
+    if all(tr is None for _, tr in downs):
+        zero = tuple(((0, 0),) * num_frames for _ in range(n_obj))
+        return None, tuple(zero if pl is None else pl for pl, _ in downs), None, None
+    return None, None, None, tuple(fulls)
 
 
 def crosses_gemm_offset_line(nb, frames, h, w, width0):
@@ -776,8 +822,19 @@ class I2VGenXLPipeline:
                 "masks": tuple(torch.stack([torch.stack([first(m[i]) for m in mk]) for mk, _ in moved]).contiguous() for i in (0, 1)),
                 "fusion_masks": [torch.stack([m[0].to(self.device, H16) for m in mk]).contiguous() for mk, _ in moved]}
 
+    def transform_variant_masks(self, masks, variant_transforms):
+        """the call's masks gathered once per variant (``transform_masks`` with each variant's transform) ->
+        dict(resample_dev = per variant the device table int32 [nobj, F, h + w] of its latent-grid maps,
+             masks = (soft, hard) fp16 [K, nobj, F, h, w] stacks for the engine (``unet.variant_masks``),
+             fusion_masks = per variant the soft masks [nobj, 1, 4, F, h, w] fp16 of the fusion steps)"""
+        moved = [self.transform_masks(masks, tr) for tr in variant_transforms]
+        first = lambda t: t.reshape(-1, *t.shape[-3:])[0].to(self.device, H16)  # as the engine forms its device masks
+        return {"resample_dev": [tab for _, tab in moved],
+                "masks": tuple(torch.stack([torch.stack([first(m[i]) for m in mk]) for mk, _ in moved]).contiguous() for i in (0, 1)),
+                "fusion_masks": [torch.stack([m[0].to(self.device, H16) for m in mk]).contiguous() for mk, _ in moved]}
+
     def make_composition_state(self, latents, cond, masks, guidance_scale, dedup_sources=None, variants=1, placement=None,
-                               variant_placements=None, transform=None):
+                               variant_placements=None, transform=None, variant_transforms=None):
         """static buffers + the captured iteration variants of the composition loop.
         cond: dict(encoder_hidden_states [n,77,D], image_embeddings [n,F,D], image_latents_first, image_latents, fps).
         The state keeps its OWN copy of ``cond``: the hoisted conditioning (``prepare_conditioning``) and the shared-CFG-prefix
@@ -794,8 +851,23 @@ class I2VGenXLPipeline:
         the fusion steps each variant's own.  The hooks keep ``masks`` as they came (shape checks and the mask key).
         ``transform`` (``normalize_obj_transforms``; not with ``placement`` / ``variant_placements``): scale, mirror
         and translation per object, one transform for all variants.  ``masks`` come in source coordinates and are gathered ONCE,
-        here, to destination coordinates (``transform_masks``); the fusion steps gather the objects' latents the same way."""
+        here, to destination coordinates (``transform_masks``); the fusion steps gather the objects' latents the same way.
+        ``variant_transforms`` (``resolve_variant_obj_transforms``; not with any of the three above): K transforms,
+        one per variant.  Each variant's masks are gathered once, here; the engine takes them as (soft, hard) [K, nobj, F, h, w]
+        stacks, the fusion steps each variant's own.  The hooks keep ``masks`` as they came (shape checks and the mask key)."""
         cond = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in cond.items()}
+        vresample = None
+        if variant_transforms is not None:
+            if placement is not None or variant_placements is not None or transform is not None:
+                raise ValueError("variant_transforms is given together with placement / variant_placements / transform: every "
+                                 "variant's transform carries its own translation, and a call transforms per variant or once")
+            if self.unet.shard is not None:
+                raise RuntimeError("variant_transforms do not combine with the frame shard: the section masks are cut to pixel "
+                                   "slabs and a gather crosses slabs")
+            if len(variant_transforms) != int(variants):
+                raise ValueError(f"variant_transforms: {len(variant_transforms)} transforms for {int(variants)} variants")
+            variant_transforms = tuple(tuple(tr) for tr in variant_transforms)
+            vresample = self.transform_variant_masks(masks, variant_transforms)
         resample_dev = None
         if transform is not None:
             if placement is not None or variant_placements is not None:
@@ -847,7 +919,8 @@ class I2VGenXLPipeline:
               "fusion_objs": torch.empty((n_obj, 1) + tuple(latents.shape[1:]), dtype=H16, device=dev), "maps": {},
               "placement": placement, "place_dev": place_dev, "place_tables": [],
               "variant_placements": variant_placements, "vplace": vstate,
-              "transform": transform, "resample_dev": resample_dev})
+              "transform": transform, "resample_dev": resample_dev,
+              "variant_transforms": variant_transforms, "vresample": vresample})
         weak = weakref.ref(st)  # (the caller holds the state for as long as it steps it)
         st["build_map"] = lambda smap: self._composition_batch(weak(), smap, do_cfg)
         st["maps"][None] = st["build_map"](None)
@@ -898,8 +971,10 @@ class I2VGenXLPipeline:
             saved_nv, u.variants = u.variants, nvar
             saved_pl, u.placement = u.placement, st["placement"]
             saved_vp, u.variant_placements = u.variant_placements, st["variant_placements"]
-            saved_vm, u.variant_masks = u.variant_masks, None if st["vplace"] is None else st["vplace"]["masks"]
+            vstate = st["vplace"] if st["vplace"] is not None else st["vresample"]
+            saved_vm, u.variant_masks = u.variant_masks, None if vstate is None else vstate["masks"]
             saved_tr, u.transform = u.transform, st["transform"]
+            saved_vt, u.variant_transforms = u.variant_transforms, st["variant_transforms"]
             try:
                 noise = u.forward_ext(inp, st["t"], mcond["fps"], mcond["image_latents_first"], mcond["image_latents"],
                                       mcond["image_embeddings"], mcond["encoder_hidden_states"], multi_frame_guidance=False,
@@ -909,6 +984,7 @@ class I2VGenXLPipeline:
                 u.placement = saved_pl
                 u.variant_placements, u.variant_masks = saved_vp, saved_vm
                 u.transform = saved_tr
+                u.variant_transforms = saved_vt
                 u.prune_background = saved_pb
             # the engine's per-level offset tables are read by this state's captured graphs: they live as long as the state,
             # also after the engine drops its cache for another placement
@@ -918,6 +994,8 @@ class I2VGenXLPipeline:
                 st["place_tables"].append(u._vplace_cache[1])
             if st["transform"] is not None and not any(d is u._resample_cache[1] for d in st["place_tables"]):
                 st["place_tables"].append(u._resample_cache[1])
+            if st["variant_transforms"] is not None and not any(d is u._vresample_cache[1] for d in st["place_tables"]):
+                st["place_tables"].append(u._vresample_cache[1])
             ops.ddim_step(x, noise[nb - nvar:nb].contiguous(), st["coef"],
                           v_uncond=noise[nb - 2 * nvar:nb - nvar].contiguous() if do_cfg else None, out=x)
 
@@ -943,6 +1021,7 @@ class I2VGenXLPipeline:
             (() if st["placement"] is None else (st["placement"],)) + \
             (() if st["variant_placements"] is None else ("variant_placements", st["variant_placements"])) + \
             (() if st.get("transform") is None else ("transform", st["transform"])) + \
+            (() if st.get("variant_transforms") is None else ("variant_transforms", st["variant_transforms"])) + \
             (("no_background",) if self.background_dead(smap) else ())
 
     def composition_step(self, st, t, bg_latents, obj_latents, table_row, fuse=None):
@@ -951,13 +1030,17 @@ class I2VGenXLPipeline:
         one conditioning class) share a chunk: the step's source map picks the batch."""
         if fuse is not None:
             mix, rnf, fobjs = fuse
-            vp = st["vplace"]
+            vp = st["vplace"] if st["vplace"] is not None else st.get("vresample")
             objs16 = [o.to(self.device, H16).contiguous() for o in fobjs] if vp is not None else None
             for k in range(st["nvar"] if vp is not None else 0):
-                # per-variant placement: K launches of the shift and of the single-variant fusion entry on the variant's slice
-                # of the latents -- its object latents moved by ITS offsets, fused with ITS (moved) masks
+                # per-variant placement / transforms: K times nobj launches of the shift (the gather) and one of the
+                # single-variant fusion entry on the variant's slice of the latents -- its object latents moved by ITS offsets
+                # (maps), fused with ITS (moved) masks
                 for j, o in enumerate(objs16):
-                    ops.shift_planes(o, vp["place_dev"][k][j], out=st["fusion_objs"][j])
+                    if st["vplace"] is not None:
+                        ops.shift_planes(o, vp["place_dev"][k][j], out=st["fusion_objs"][j])
+                    else:
+                        ops.gather_planes(o, vp["resample_dev"][k][j], out=st["fusion_objs"][j])
                 lat = st["latents"][k:k + 1]
                 ops.latent_fusion(lat, bg_latents, st["fusion_objs"], vp["fusion_masks"][k], mix, rnf, out=lat)
             for j, o in enumerate(fobjs if vp is None else ()):
@@ -1003,7 +1086,7 @@ class I2VGenXLPipeline:
             fusion_steps=(0, 3), ddim_init_latents_t_idx=1, ddim_inv_prompt=None, obj_mask=None, obj_width_height=None,
             obj_ddim_latents_idx_offset=None, obj_random_noise_fusion=False, random_noise_ratio=0.0,
             bg_inv_latents_path=None, obj_ddim_latents_path=None, obj_masks_tensors=None, obj_offsets=None,
-            variant_obj_offsets=None, obj_transforms=None):
+            variant_obj_offsets=None, obj_transforms=None, variant_obj_transforms=None):
         """PnP composition sampling.  ``obj_mask``: list of mask paths (preprocessed by ``mvoc_amd.utils.mask_preprocess``)
         or pass ``obj_masks_tensors`` = list of (float [1,4,F,h,w], bool [1,4,F,h,w]) directly.
 
@@ -1026,7 +1109,12 @@ class I2VGenXLPipeline:
         ``flip`` (None, "h", "v", "hv") and ``anchor`` ([ax, ay], image pixels in multiples of 4; default the frame centre) --
         the object is scaled and mirrored about the anchor (nearest neighbour, exact) and then moved, without re-inverting
         anything (``normalize_obj_transforms``; shared by the variants, not with a frame shard).  Every object at identity:
-        exactly a call without it; translation only: exactly the ``obj_offsets`` call.  ``obj_width_height`` stays ignored."""
+        exactly a call without it; translation only: exactly the ``obj_offsets`` call.  ``obj_width_height`` stays ignored.
+
+        ``variant_obj_transforms`` (not together with any of the three above): a list of K items, one per variant,
+        each None or a value ``obj_transforms`` accepts -- variant k composes the objects under ITS transform over the one set
+        of source chunks (``resolve_variant_obj_transforms``).  All items identity: exactly a call without it; all items equal:
+        exactly the ``obj_transforms`` call; translations only: exactly the ``variant_obj_offsets`` call."""
         from .utils import mask_preprocess
         # ---- the variants of this call (one with scalar arguments: the batch, kernels and launches of a single composition)
         m_rep = int(num_videos_per_prompt)
@@ -1074,6 +1162,10 @@ class I2VGenXLPipeline:
         if obj_transforms is not None and (obj_offsets is not None or variant_obj_offsets is not None):
             raise ValueError("obj_transforms is given together with obj_offsets / variant_obj_offsets: a transform carries its "
                              "own offset, and one transform serves all variants")
+        if variant_obj_transforms is not None and (obj_transforms is not None or obj_offsets is not None
+                                                   or variant_obj_offsets is not None):
+            raise ValueError("variant_obj_transforms is given together with obj_transforms / obj_offsets / variant_obj_offsets: "
+                             "every variant's transform carries its own offset, and a call transforms per variant or once")
         placement = normalize_obj_offsets(obj_offsets, n_obj, num_frames, self.vae_scale_factor)
         variant_placements = None
         if variant_obj_offsets is not None:
@@ -1083,6 +1175,14 @@ class I2VGenXLPipeline:
         if obj_transforms is not None:
             placement, transform = normalize_obj_transforms(obj_transforms, n_obj, num_frames, height // self.vae_scale_factor,
                                                             width // self.vae_scale_factor, self.vae_scale_factor)
+        variant_transforms = None
+        if variant_obj_transforms is not None:
+            placement, variant_placements, transform, variant_transforms = resolve_variant_obj_transforms(
+                variant_obj_transforms, nvar, n_obj, num_frames, height // self.vae_scale_factor, width // self.vae_scale_factor,
+                self.vae_scale_factor)
+        if variant_transforms is not None and self.unet.shard is not None:
+            raise RuntimeError("variant_obj_transforms do not combine with the frame shard: the section masks are cut to pixel "
+                               "slabs and a gather crosses slabs")
         if transform is not None and self.unet.shard is not None:
             raise RuntimeError("obj_transforms do not combine with the frame shard: the section masks are cut to pixel slabs and a "
                                "gather crosses slabs")
@@ -1176,7 +1276,8 @@ class I2VGenXLPipeline:
         st = self.make_composition_state(latents, cond, obj_masks_tensors, scales if nvar > 1 else guidance_scale, variants=nvar,
                                          **({} if placement is None else {"placement": placement}),
                                          **({} if variant_placements is None else {"variant_placements": variant_placements}),
-                                         **({} if transform is None else {"transform": transform}))
+                                         **({} if transform is None else {"transform": transform}),
+                                         **({} if variant_transforms is None else {"variant_transforms": variant_transforms}))
         table, index = sched.coef_table(self.device, guidance_scale)
         if nvar > 1:  # [steps, K, 5]: a step's coefficient rows are one view, whatever K is
             table = torch.stack([sched.coef_table(self.device, g)[0] for g in scales], 1).contiguous()

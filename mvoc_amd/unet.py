@@ -706,6 +706,14 @@ class I2VGenXLUNet:
         # frame shard.
         self.transform = None
         self._resample_cache = (None, {})
+        # Per-variant transforms (pipeline.py variant_obj_transforms): None, or a hashable tuple of K = ``variants``
+        # transforms in the format of ``transform`` (a variant that is not transformed carries the identity: scale 1/1, no flip,
+        # anchor at the frame centre, zero offsets).  Every injection site then passes ``variant_masks`` -- variant k's masks
+        # gathered with ITS maps -- and the per-level [K, nobj, F, H + W] table to the _resampled_variants blend entries.  Set and
+        # restored around its forward by the composition loop, like variant_placements; not together with placement /
+        # variant_placements / transform, not with a frame shard.
+        self.variant_transforms = None
+        self._vresample_cache = (None, {})
 
     def set_frame_shard(self, shard):
         """Frame-shard every forward over the ranks of ``shard`` (``mvoc_amd.frame_shard``): each rank receives the FULL
@@ -945,12 +953,14 @@ class I2VGenXLUNet:
 
     def site_masks(self, masks, kind):
         """the masks a site's blend reads (kind 0 = soft, 1 = hard): ``masks`` [nobj, F, h, w] of the hook state, or under
-        ``variant_placements`` the [K, nobj, F, h, w] stack of ``variant_masks`` (checked against the hook masks' shape)"""
-        if self.variant_placements is None:
+        ``variant_placements`` / ``variant_transforms`` the [K, nobj, F, h, w] stack of ``variant_masks`` (checked against the
+        hook masks' shape)"""
+        if self.variant_placements is None and self.variant_transforms is None:
             return masks
         vm = self.variant_masks
         if vm is None:
-            raise RuntimeError("variant_placements is set but variant_masks is not: the engine needs the (soft, hard) "
+            which = "variant_placements" if self.variant_placements is not None else "variant_transforms"
+            raise RuntimeError(f"{which} is set but variant_masks is not: the engine needs the (soft, hard) "
                                "[K, nobj, F, h, w] mask stacks of the placed variants")
         stack = vm[kind]
         if stack.dim() != 5 or stack.shape[0] != self.variants or tuple(stack.shape[1:]) != tuple(masks.shape):
@@ -979,9 +989,35 @@ class I2VGenXLUNet:
             tab = self._resample_cache[1][key] = ops.resample_table(tr, H, W, mh, mw, self.device)
         return tab
 
+    def variant_resample_table(self, mask_list, H, W):
+        """the ``resample=`` argument under ``variant_transforms``: the device table [K, nobj, F, H + W] of this H x W, cached per
+        (variant_transforms, H, W, mh, mw) and dropped when the transforms change"""
+        vt = self.variant_transforms
+        if self.placement is not None or self.variant_placements is not None or self.transform is not None:
+            raise RuntimeError("variant_transforms is set together with placement / variant_placements / transform: every "
+                               "variant's transform carries its own translation, and a call transforms per variant or once")
+        if self.shard is not None:
+            raise RuntimeError("variant_transforms do not combine with the frame shard: the section masks are cut to pixel "
+                               "slabs and a gather crosses slabs")
+        if len(vt) != self.variants:
+            raise RuntimeError(f"variant_transforms holds {len(vt)} transforms, the call {self.variants} variants")
+        for k, tr in enumerate(vt):
+            if len(tr) != len(mask_list):
+                raise RuntimeError(f"variant_transforms[{k}] holds {len(tr)} objects, the hooks carry {len(mask_list)} masks")
+        if self._vresample_cache[0] != vt:
+            self._vresample_cache = (vt, {})
+        mh, mw = self._all_frame_masks(mask_list)[0].shape[2:]
+        key = (H, W, mh, mw)
+        tab = self._vresample_cache[1].get(key)
+        if tab is None:
+            tab = self._vresample_cache[1][key] = ops.resample_table_variants(vt, H, W, mh, mw, self.device)
+        return tab
+
     def place_kw(self, mask_list, H, W):
         """keyword arguments of a site's blend call: none without a placement or transform (exactly today's call), else
-        ``place=`` -- or, under ``transform``, ``resample=`` the level's table"""
+        ``place=`` -- or, under ``transform`` / ``variant_transforms``, ``resample=`` the level's table"""
+        if self.variant_transforms is not None:
+            return {"resample": self.variant_resample_table(mask_list, H, W)}
         if self.transform is not None:
             return {"resample": self.resample_table(mask_list, H, W)}
         tab = self.place_table(mask_list, H, W)
@@ -992,6 +1028,9 @@ class I2VGenXLUNet:
         if self.transform is not None and self.shard is not None:
             raise RuntimeError("a transform does not combine with the frame shard: the section masks are cut to pixel slabs "
                                "and a gather crosses slabs")
+        if self.variant_transforms is not None and self.shard is not None:
+            raise RuntimeError("variant_transforms do not combine with the frame shard: the section masks are cut to pixel "
+                               "slabs and a gather crosses slabs")
         if self.placement is not None and self.shard is not None:
             raise RuntimeError("a placement does not combine with the frame shard: the section masks are cut to pixel slabs "
                                "and a shift crosses slabs")
@@ -1014,7 +1053,7 @@ class I2VGenXLUNet:
             chunks = tuple(range(nsrc)) if smap is None else tuple(c - 1 for c in smap[1])
             ndst = self.check_pnp_batch(B, mask_list, nsrc, self.variants, no_background=True)
             positional = smap is None and self.variants == 1 and self.placement is None and self.variant_placements is None \
-                and self.transform is None
+                and self.transform is None and self.variant_transforms is None
             return ndst, (None if positional else (nsrc, chunks))
         return self.check_pnp_batch(B, mask_list, None if smap is None else smap[0], self.variants), smap
 

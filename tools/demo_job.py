@@ -26,6 +26,9 @@ anchor, then the offset.  Reported like --place.
 --variant-place "dx,dy;dx,dy|dx,dy;dx,dy|.." (opt-in, needs --variants K): K placements separated by `|`, each in the format of
 --place -- the variants' `placement` key: every variant composes the objects at its own offsets over the one set
 of source chunks.  With --sequential the K single jobs each take their variant's placement as `obj_offset`.
+--variant-transform "scale=3/2,flip=h;scale=1/2||offset=64,0;" (opt-in, needs --variants K): K transforms separated by `|`, each
+in the format of --transform -- the variants' `transform` key; an empty item leaves that variant untransformed.
+With --sequential the K single jobs each take their variant's transform as `obj_transform`.
 
 --shared-source (opt-in): the shape of MVOC's own demo entries, where the background and both objects point at ONE inversion
 directory and the same control frames.  One clip is inverted, then the composition runs with source de-duplication off and then
@@ -423,8 +426,27 @@ def parse_variant_place(text, variants):
     return out
 
 
+def parse_variant_transform(text, variants):
+    """"scale=3/2,flip=h;scale=1/2||offset=64,0;" -> K transforms, each as ``parse_transform`` returns it (`|` separates the
+    variants); an empty item is None: that variant is not transformed"""
+    if not variants:
+        raise SystemExit("--variant-transform needs --variants K (one transform per variant)")
+    items = text.split("|")
+    if len(items) != variants:
+        raise SystemExit(f"--variant-transform {text!r}: {len(items)} transforms for {variants} variants")
+    out = []
+    for k, item in enumerate(items):
+        try:
+            out.append(parse_transform(item) if item.strip() else None)
+        except SystemExit as e:
+            raise SystemExit(f"--variant-transform, variant {k}: {e}")
+    if len({len(t) for t in out if t is not None}) > 1:
+        raise SystemExit(f"--variant-transform {text!r}: every transformed variant needs one item per object")
+    return out
+
+
 def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, thresholds=None, sequential=False, place=None,
-                 variant_place=None, transform=None):
+                 variant_place=None, transform=None, variant_transform=None):
     """K prompts and seeds over the boat_surf-shaped job (three distinct sources), one composition loop (composite.py `variants`).
     ``thresholds``: K values of pnp_spatial_attn_t, one per variant (the variants' `pnp` key); ``sequential``: after
     the one loop, the same K compositions one by one (single entries with the flat threshold) for the comparison."""
@@ -461,6 +483,12 @@ def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, threshol
             raise SystemExit(f"--variant-place: {len(variant_place)} placements for {variants} variants")
         for v, p in zip(var, variant_place):
             v["placement"] = [list(q) for q in p]
+    if variant_transform is not None:  # the variants' own transforms; None: that variant is not transformed
+        if len(variant_transform) != variants:
+            raise SystemExit(f"--variant-transform: {len(variant_transform)} transforms for {variants} variants")
+        for v, t in zip(var, variant_transform):
+            if t is not None:
+                v["transform"] = [dict(o) for o in t]
     centry = dict(boat_surf_entry(size), variants=var)
     if place is not None:  # shared by the variants: an entry key
         centry["obj_offset"] = [list(p) for p in place]
@@ -482,6 +510,8 @@ def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, threshol
         res["variant_placement"] = [[list(q) for q in p] for p in variant_place]
     if transform is not None:
         res["obj_transform"] = [dict(t) for t in transform]
+    if variant_transform is not None:
+        res["variant_transform"] = [None if t is None else [dict(o) for o in t] for t in variant_transform]
     if thresholds is not None:
         res["variant_thresholds"] = [float(t) for t in thresholds]
         res["output_suffix_of"] = {d: where[d] for d in dirs}
@@ -489,13 +519,15 @@ def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, threshol
         seq = []
         for k in range(variants):
             e = dict(boat_surf_entry(size), edited_video_name=f"seq{k}",
-                     **{kk: vv for kk, vv in var[k].items() if kk not in ("pnp", "placement")})
+                     **{kk: vv for kk, vv in var[k].items() if kk not in ("pnp", "placement", "transform")})
             if place is not None:
                 e["obj_offset"] = [list(p) for p in place]
             if variant_place is not None:  # the single job of variant k: its placement as the entry's
                 e["obj_offset"] = [list(q) for q in variant_place[k]]
             if transform is not None:
                 e["obj_transform"] = [dict(t) for t in transform]
+            if variant_transform is not None and variant_transform[k] is not None:  # the single job of variant k: its transform as the entry's
+                e["obj_transform"] = [dict(o) for o in variant_transform[k]]
             if thresholds is not None:
                 e["pnp_spatial_attn_t"] = float(thresholds[k])
             with StageTimer(pl) as t1:
@@ -537,15 +569,19 @@ if __name__ == "__main__":
                     help="with --variants K: K placements separated by |, each in the format of --place (the variants' `placement` key)")
     ap.add_argument("--transform", type=str, default=None, metavar="scale=p/q,flip=h,offset=dx,dy;..",
                     help="scale / mirror / place the objects at composition time: one item per object separated by ; (`obj_transform`)")
+    ap.add_argument("--variant-transform", type=str, default=None, metavar="scale=p/q,flip=h;..|..",
+                    help="with --variants K: K transforms separated by |, each in the format of --transform (the variants' "
+                         "`transform` key); an empty item leaves that variant untransformed")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
-    if a.variants or a.place or a.variant_place or a.transform:
+    if a.variants or a.place or a.variant_place or a.transform or a.variant_transform:
         th = None if a.variant_thresholds is None else [float(x) for x in a.variant_thresholds.split(",")]
         place = None if a.place is None else parse_place(a.place)
         vplace = None if a.variant_place is None else parse_variant_place(a.variant_place, a.variants)
         transform = None if a.transform is None else parse_transform(a.transform)
-        print(json.dumps(run_variants(a.frames, a.size, a.steps, a.keep, a.variants or 1, th, a.sequential, place, vplace, transform)),
-              flush=True)
+        vtransform = None if a.variant_transform is None else parse_variant_transform(a.variant_transform, a.variants)
+        print(json.dumps(run_variants(a.frames, a.size, a.steps, a.keep, a.variants or 1, th, a.sequential, place, vplace, transform,
+                                      vtransform)), flush=True)
     else:
         fn = run_shared_source if a.shared_source else run
         print(json.dumps(fn(a.frames, a.size, a.steps, a.keep)), flush=True)
