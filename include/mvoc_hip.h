@@ -43,7 +43,8 @@ typedef struct mvoc_gemm_desc {
   /* operands */
   const void* a;        /* activation source 1 (fp16) */
   const void* a2;       /* optional source 2 for a channel-concat input (cat([x, skip], dim=1)); NULL if none */
-  const void* w;        /* weights [n_pad][k] fp16, k contiguous; for conv k = tap*cin + c (tap-major; k_order = 1: chunk-major, below) */
+  const void* w;        /* weights [n][k] fp16 (upsample == 2: [4 n][k]), k contiguous, no row beyond n is needed; for conv k = tap*cin + c
+                           (tap-major; k_order = 1: chunk-major, below) */
   void* out;            /* [m][ldo] fp16 */
   const void* bias;     /* [n] fp16 or NULL (GEGLU: packed like w rows) */
   const void* rowadd;   /* optional [m / rowadd_div][ld_rowadd] fp16 added per output row (time embedding) */
@@ -120,6 +121,23 @@ typedef struct mvoc_gemm_desc {
                            tap-major weights for those launches. */
 } mvoc_gemm_desc;
 
+/* Extents (enforced by tests/test_gemm_contract_gpu.py on every tile id, on allocations whose undescribed elements are NaN; cols =
+ * n_store, or n where n_store is 0, GEGLU: n / 2; rows_a = nimg hsrc wsrc for conv3x3, else m):
+ *   - only these elements influence a result: a[rows_a][c1] at pitch lda and a2[rows_a][cin - c1] at pitch lda2 (plain: cin = k),
+ *     w[n][k] (upsample == 2: [4 n][k]), bias[n], rowadd[ceil(m / rowadd_div)][cols] at pitch ld_rowadd, resid[m][cols] at pitch ldr,
+ *     ln_rowsum[n], ln_bias[n], ln_stats[m][2].  The columns of a / a2 at and past c1 / cin - c1 (the column views taken of fused
+ *     projections), the residual's and the row-add's columns at and past cols and the gaps between their rows, whatever lies around
+ *     any operand, and the prior contents of the workspace never do, whatever they hold;
+ *   - conv3x3 with k > 9 cin (the K of the small-channel convs, padded to a multiple of 32): the columns of w at and past 9 cin ARE
+ *     described and must hold zeros, as mvoc_amd.unet.pack_conv3x3 writes them: the kernels zero the activation side there and still
+ *     multiply, so a NaN or an infinity in them reaches the result;
+ *   - no byte of out outside [m][cols] at pitch ldo is written, no byte of the workspace past split_k * m * n * 4, and none of the
+ *     input operands;
+ *   - chan_sums and row_moments: either the query function below answers non-zero and exactly [m / 256][cols][2], respectively the
+ *     entries [m][ceil(n / w)][2] of rows of row_moments_ld entries, are written (the further entries of a row are not), or it
+ *     answers 0 and no byte of the operand is written.  After a call that returns non-zero both answer 0;
+ *   - the return value is always one of 0, -1, -2, -3 (top of this file), with the text in mvoc_last_error(); a refused call
+ *     writes nothing. */
 int mvoc_gemm_f16(const mvoc_gemm_desc* d, void* stream);
 /* 1 when this thread's most recent mvoc_gemm_f16 call wrote its descriptor's chan_sums */
 int mvoc_gemm_chan_sums_written(void);

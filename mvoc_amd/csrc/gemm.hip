@@ -898,9 +898,8 @@ bool sums_reduce_ok(const mvoc_gemm_desc* d) {
   return d->ldo % 4 == 0 && ((uintptr_t)d->out & 7) == 0 && (!d->resid || (d->ldr % 4 == 0 && ((uintptr_t)d->resid & 7) == 0)) &&
          (!d->rowadd || (d->ld_rowadd % 4 == 0 && ((uintptr_t)d->rowadd & 7) == 0));
 }
-}  // namespace
 
-extern "C" int mvoc_gemm_f16(const mvoc_gemm_desc* d, void* stream) {
+int gemm_dispatch(const mvoc_gemm_desc* d, void* stream) {
   g_sums_written = 0;
   g_rowmom_bx = 0;
   MVOC_REQUIRE(d && d->a && d->w && d->out, -1, "gemm: null operand");
@@ -1205,4 +1204,11 @@ extern "C" int mvoc_gemm_f16(const mvoc_gemm_desc* d, void* stream) {
       return launch_glds<1, 4, 5, 2, 2, 0, 32>(a, s);  // 160 x 256
     default: mvoc_set_error("gemm: unknown tile %d", tile); return -1;
   }
+}
+}  // namespace
+
+extern "C" int mvoc_gemm_f16(const mvoc_gemm_desc* d, void* stream) {
+  const int rc = gemm_dispatch(d, stream);
+  if (rc != 0) g_sums_written = g_rowmom_bx = 0;  // a refused or failed call answers 0 to both query functions, whatever was decided on the way
+  return rc;
 }

@@ -851,19 +851,28 @@ int launch8(const GemmArgs& a0, hipStream_t s) {
     return -2;
   }
   if constexpr (KO) {
-    if (epi != 1) return -9;  // (conv / temporal conv: bias, row-add, residual)
+    if (epi != 1) {  // (conv / temporal conv: bias, row-add, residual; gemm.hip refuses anything else before it gets here)
+      mvoc_set_error("gemm8: k_order = 1 exists with the plain epilogue only");
+      return -2;
+    }
     hipLaunchKernelGGL((gemm8_kernel<XT, RETAIN, YP, UPS, AFF, 1, true>), dim3((unsigned)nblk), dim3(512), 0, s, a);
   } else if constexpr (UPS) {
     // the folded-upsample form exists with the plain epilogue only (Upsample2D's conv: bias): its other epilogue forms spilled
     // registers once the sub-pixel gather joined it, and no caller has them (gemm.hip sends such a request to the general tiles)
-    if (epi != 1) return -9;
+    if (epi != 1) {  // (gemm.hip: g8_ok refuses an upsample with an activation or a LayerNorm fold)
+      mvoc_set_error("gemm8: the folded-upsample form exists with the plain epilogue only");
+      return -2;
+    }
     hipLaunchKernelGGL((gemm8_kernel<XT, RETAIN, YP, UPS, AFF, 1>), dim3((unsigned)nblk), dim3(512), 0, s, a);
   } else {
     if (epi == 1) hipLaunchKernelGGL((gemm8_kernel<XT, RETAIN, YP, UPS, AFF, 1>), dim3((unsigned)nblk), dim3(512), 0, s, a);
     else if (epi == 2) hipLaunchKernelGGL((gemm8_kernel<XT, RETAIN, YP, UPS, AFF, 2>), dim3((unsigned)nblk), dim3(512), 0, s, a);
     else if (epi == 3) hipLaunchKernelGGL((gemm8_kernel<XT, RETAIN, YP, UPS, AFF, 3>), dim3((unsigned)nblk), dim3(512), 0, s, a);
     else if constexpr (XT == 4) hipLaunchKernelGGL((gemm8_kernel<XT, RETAIN, YP, UPS, AFF, 0>), dim3((unsigned)nblk), dim3(512), 0, s, a);
-    else return -9;  // (unreachable: mvoc_launch_gemm8 sends the general epilogue of a 320-wide request to the 256-wide tile)
+    else {  // (mvoc_launch_gemm8 sends the general epilogue of a 320-wide request to the 256-wide tile)
+      mvoc_set_error("gemm8: the 320-wide tile has no general epilogue");
+      return -2;
+    }
   }
   return mvoc_check_launch("gemm8_kernel");
 }
@@ -896,7 +905,6 @@ int mvoc_launch_gemm8(const GemmArgs& a, int bx, hipStream_t s, int* bx_used) {
       used = 320;
       if (a.korder) {
         // chunk-major K (gemm_args.h: korder): the 320-wide plain-epilogue form only -- gemm.hip sends nothing else here
-        if (a.ln_s) return -9;
         return launch8<5, false, false, false, true, true>(a, s);
       }
       return launch8<5, false, false, false, true>(a, s);
