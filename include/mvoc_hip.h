@@ -329,6 +329,10 @@ int mvoc_layernorm_f16(const void* x, const void* gamma, const void* beta, void*
  *   nchw:   x [5F, C, H, W] (pnp_utils.py:970-1004, 1059-1082, 1114-1146): p contiguous
  * masks: [nobj][F][mh][mw] fp16, nearest-resized to (H, W) like F.interpolate(mode='nearest').
  * Up to two tensors (Q and K) are processed by one launch (x2 may be NULL).
+ * Alignment: the tokens entries read and write 16-byte vectors and return -2 with an error text (nothing launched) unless x
+ * and x2 are 16-byte aligned (channels and the three strides are multiples of 8 already); the nchw entries take any 2-byte
+ * aligned x / x2 and run 8 pixels per work item when H*W is a multiple of 8 and both pointers are 16-byte aligned, else one.
+ * Masks need 2-byte and tables 4-byte alignment.
  * ------------------------------------------------------------------------------------------- */
 typedef struct mvoc_pnp_desc {
   void* x;

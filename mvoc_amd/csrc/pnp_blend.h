@@ -392,7 +392,7 @@ struct Launch {
   dim3 grid;
   hipStream_t s;
   int ntens;
-  bool vec;              // nchw: 8 pixels per work item (H * W a multiple of 8); tokens: always 8 channels
+  bool vec;              // nchw: 8 pixels per work item (H * W a multiple of 8, x / x2 16-byte aligned); tokens: always 8 channels
   double elems, pixels;  // F * H * W * C and F * H * W
 };
 
@@ -410,6 +410,8 @@ int finish_prepare(const mvoc_pnp_desc* d, const PnpArgs& a, void* stream, Launc
 int prepare_tokens(const mvoc_pnp_desc* d, PnpArgs& a, void* stream, Launch& l) {
   MVOC_REQUIRE(d->channels % 8 == 0 && d->chunk_stride % 8 == 0 && d->f_stride % 8 == 0 && d->p_stride % 8 == 0, -2,
                "pnp tokens: channels/strides must be multiples of 8");
+  // every access of the tokens kernels is a 16-byte vector at x + a multiple of 8 elements
+  MVOC_REQUIRE(((uintptr_t)d->x | (uintptr_t)d->x2) % 16 == 0, -2, "pnp tokens: x and x2 must be 16-byte aligned");
   l.vec = true;
   a.total = (long)d->frames * d->height * d->width * (d->channels / 8);
   return finish_prepare(d, a, stream, l, "pnp tokens: grid too large");
@@ -417,7 +419,8 @@ int prepare_tokens(const mvoc_pnp_desc* d, PnpArgs& a, void* stream, Launch& l) 
 
 int prepare_nchw(const mvoc_pnp_desc* d, PnpArgs& a, void* stream, Launch& l) {
   const long hw = (long)d->height * d->width;
-  l.vec = hw % 8 == 0;
+  // the 8-wide form reads and writes 16-byte vectors at x + a multiple of 8 elements: it needs the pointers aligned as well
+  l.vec = hw % 8 == 0 && ((uintptr_t)d->x | (uintptr_t)d->x2) % 16 == 0;
   a.total = (long)d->frames * d->channels * (l.vec ? hw / 8 : hw);
   return finish_prepare(d, a, stream, l, "pnp nchw: grid too large");
 }
