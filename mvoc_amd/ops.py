@@ -501,7 +501,7 @@ def _pnp_desc(x, x2, masks, chunk_stride, f_stride, p_stride, frames, height, wi
     if masks.dim() == 5 and masks.is_contiguous() and masks.shape[2] == frames:
         # per-variant placement: a [K, nobj, F, mh, mw] stack.  The descriptor has no field for K: it takes the
         # stack's pointer (variant 0 first) and one variant's dims; K and the stack's shape are checked against the 4-D table by
-        # _check_place_variants, and both blend functions refuse a stack that comes without such a table before any launch
+        # _check_table, and both blend functions refuse a stack that comes without such a table before any launch (_blend_entry)
         masks = masks[0]
     if masks.dim() != 4 or not masks.is_contiguous() or masks.shape[1] != frames:
         raise RuntimeError(f"pnp: masks must be contiguous [nobj, F, mh, mw] fp16, got {tuple(masks.shape)}")
@@ -549,36 +549,69 @@ def _active_mask(active, nvar, what):
     return None if active == (1 << nvar) - 1 else active
 
 
-def _pnp_blend(layout, d, x, x2, masks, need, ndst, src_map, nvar, active, place, resample):
-    """pick the library entry mvoc_pnp_blend_scatter_<layout><suffix> for the arguments of ``pnp_blend_<layout>`` and call it on
-    the descriptor ``d``; ``need(nchunk)``: elements a tensor must hold from its first for a batch of nchunk chunks"""
-    what = f"pnp_blend_{layout}"
+def _blend_entry(what, place, resample, mask_dim, no_background, src_map, nvar, active):
+    """the suffix of the library entry mvoc_pnp_blend_scatter_<layout><suffix> that the arguments of ``pnp_blend_<layout>``
+    select, by the form of ``place`` / ``resample`` (None, a 3-D table shared by the variants, a 4-D table per variant) and of the
+    masks (4-D, or a 5-D [K, nobj, F, mh, mw] stack, which goes with a 4-D table only); every other combination is refused"""
+    dim = lambda t: t.dim() if torch.is_tensor(t) else None
+    if resample is not None:
+        if place is not None:
+            raise RuntimeError(f"{what}: resample= and place= are both given: a translation is part of the resample table")
+        if mask_dim == 5 and dim(resample) != 4:
+            raise RuntimeError(f"{what}: resample= does not take a [K, nobj, F, mh, mw] mask stack: one transform serves all variants")
+        if no_background:
+            raise RuntimeError(f"{what}: resample= with no_background: pass src_map=(nobj, range(nobj)) instead")
+        return "_resampled_variants" if dim(resample) == 4 else "_resampled"
+    if mask_dim == 5 and dim(place) != 4:
+        raise RuntimeError(f"{what}: a [K, nobj, F, mh, mw] mask stack needs place= as an int32 [K, nobj, F, 2] table")
+    if place is not None:
+        return "_placed_variants" if dim(place) == 4 else "_placed"
+    if nvar == 1:
+        return "" if src_map is None else "_mapped"
+    return "_variants" if active is None else "_variants_sel"
 
-    def call(suffix, *args):
+
+def _check_table(what, name, table, masks, nvar, d):
+    """the form of a ``place`` ([.., 2]) or ``resample`` ([.., H + W]) table against the descriptor: int32 [nobj, F, ..], or per
+    variant [K, nobj, F, ..] next to a [K, nobj, F, mh, mw] mask stack"""
+    _chk(table, name, torch.int32)
+    last, size = ("2", 2) if name == "place" else ("H + W", d.height + d.width)
+    shape, dims = (d.nobj, d.frames, size), f"nobj = {d.nobj}, F = {d.frames}"
+    if table.dim() == 4:
+        shape, dims = (int(nvar),) + shape, f"K = {int(nvar)}, " + dims
+    if tuple(table.shape) != shape or not table.is_contiguous():
+        raise RuntimeError(f"{what}: {name} must be a contiguous int32 [{dims}, {last if name == 'place' else f'H + W = {size}'}] table"
+                           f"{' with a [K, nobj, F, mh, mw] mask stack' if table.dim() == 4 else ''}, got {tuple(table.shape)}")
+    if table.dim() == 4 and (masks.dim() != 5 or tuple(masks.shape[:3]) != shape[:3] or not masks.is_contiguous()):
+        raise RuntimeError(f"{what}: a [K, nobj, F, {last}]{' resample' if name == 'resample' else ''} table needs masks as a "
+                           f"contiguous [{dims}, mh, mw] stack, got {tuple(masks.shape)}")
+
+
+def _pnp_blend(layout, d, x, x2, masks, need, ndst, src_map, nvar, active, place, resample, no_background=False):
+    """call the library entry mvoc_pnp_blend_scatter_<layout><suffix> that the arguments of ``pnp_blend_<layout>`` select
+    (``_blend_entry``) on the descriptor ``d``; ``need(nchunk)``: elements a tensor must hold from its first for a batch of
+    nchunk chunks"""
+    what = f"pnp_blend_{layout}"
+    suffix = _blend_entry(what, place, resample, masks.dim(), no_background, src_map, nvar, active)
+
+    def call(*args):
         name = f"pnp_blend_scatter_{layout}{suffix}"
         check(getattr(lib, "mvoc_" + name)(C.byref(d), *args, _stream()), name)
 
-    per_variant_maps = resample is not None and _check_resample_variants(resample, masks, nvar, d.nobj, d.frames, d.height,
-                                                                         d.width, what)
-    if masks.dim() == 5 and not per_variant_maps and (place is None or place.dim() != 4):
-        raise RuntimeError(f"{what}: a [K, nobj, F, mh, mw] mask stack needs place= as an int32 [K, nobj, F, 2] table")
-    if nvar == 1 and place is None and resample is None:
-        return call("") if src_map is None else call("_mapped", *_src_map_args(src_map, d.nobj))
+    if suffix == "":
+        return call()
+    if suffix == "_mapped":
+        return call(*_src_map_args(src_map, d.nobj))
     nsrc, chunks = _variant_map(src_map, d.nobj)
     _check_variants(x, x2, nvar, need(nsrc + (int(ndst) or 2) * int(nvar)), what)
-    if per_variant_maps:
-        return call("_resampled_variants", nsrc, chunks, int(nvar), _all_or(active, nvar), resample.data_ptr())
-    if resample is not None:
-        _check_resample(resample, d.nobj, d.frames, d.height, d.width, what)
-        return call("_resampled", nsrc, chunks, int(nvar), _all_or(active, nvar), resample.data_ptr())
-    if _check_place_variants(place, masks, nvar, d.nobj, d.frames, what):
-        return call("_placed_variants", nsrc, chunks, int(nvar), _all_or(active, nvar), place.data_ptr())
-    if place is not None:
-        _check_place(place, d.nobj, d.frames, what)
-        return call("_placed", nsrc, chunks, int(nvar), _all_or(active, nvar), place.data_ptr())
-    if active is not None:
-        return call("_variants_sel", nsrc, chunks, int(nvar), active)
-    return call("_variants", nsrc, chunks, int(nvar))
+    if suffix == "_variants":
+        return call(nsrc, chunks, int(nvar))
+    if suffix == "_variants_sel":
+        return call(nsrc, chunks, int(nvar), active)
+    # a table: the _placed / _resampled entries take the bitmask in every case (all bits: every variant injects)
+    name, table = ("place", place) if place is not None else ("resample", resample)
+    _check_table(what, name, table, masks, nvar, d)
+    return call(nsrc, chunks, int(nvar), _all_or(active, nvar), table.data_ptr())
 
 
 def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride, f_stride, p_stride, x2=None,
@@ -598,8 +631,6 @@ def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride,
     entry, whatever ``nvar`` / ``src_map`` / ``active`` are.  Not with ``place``, not with a per-variant mask stack.
     A 4-D ``resample`` (``resample_table_variants``) with a [K, nobj, F, mh, mw] mask stack: a transform and masks
     per variant -- the ``_resampled_variants`` entry."""
-    if resample is not None:
-        _refuse_resample_mix(place, masks, no_background, "pnp_blend_tokens", resample)
     d = _pnp_desc(x, x2, masks, chunk_stride, f_stride, p_stride, frames, height, width, channels, base_chunk0, ndst)
     active = _active_mask(active, nvar, "pnp_blend_tokens")
     if no_background:
@@ -613,7 +644,7 @@ def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride,
         d.base_chunk0 = -1  # (include/mvoc_hip.h: no background chunk, the base is the last chunk)
     reach = (frames - 1) * f_stride + (height * width - 1) * p_stride + channels  # of the last chunk's last element
     _pnp_blend("tokens", d, x, x2, masks, lambda nchunk: (nchunk - 1) * chunk_stride + reach, ndst, src_map, nvar, active, place,
-               resample)
+               resample, no_background)
     return x
 
 
@@ -624,8 +655,6 @@ def pnp_blend_nchw(x, masks, *, frames, x2=None, base_chunk0=True, ndst=2, src_m
     written, ``place`` moves the objects, ``resample`` scales / mirrors / moves them (see ``pnp_blend_tokens``)."""
     if x.dim() != 4 or not x.is_contiguous():
         raise RuntimeError("pnp_blend_nchw: x must be contiguous [N, C, H, W]")
-    if resample is not None:
-        _refuse_resample_mix(place, masks, False, "pnp_blend_nchw", resample)
     d = _pnp_desc(x, x2, masks, 0, 0, 0, frames, x.shape[2], x.shape[3], x.shape[1], base_chunk0, ndst)
     active = _active_mask(active, nvar, "pnp_blend_nchw")
     _pnp_blend("nchw", d, x, x2, masks, lambda nchunk: nchunk * frames * x[0].numel(), ndst, src_map, nvar, active, place, resample)
@@ -659,12 +688,6 @@ def place_table(placement, height, width, mask_h, mask_w, device):
     return torch.tensor(lv, dtype=torch.int32).to(device).contiguous()
 
 
-def _check_place(place, nobj, frames, what):
-    _chk(place, "place", torch.int32)
-    if tuple(place.shape) != (nobj, frames, 2) or not place.is_contiguous():
-        raise RuntimeError(f"{what}: place must be a contiguous int32 [nobj = {nobj}, F = {frames}, 2] table, got {tuple(place.shape)}")
-
-
 def place_table_variants(placements, height, width, mask_h, mask_w, device):
     """the device table the ``_placed_variants`` blend entries read: int32 [K, nobj, F, 2], row k = ``place_table`` of
     ``placements[k]`` (the same rule, ``level_offset``, and the same int32 refusal)"""
@@ -679,22 +702,6 @@ def place_table_variants(placements, height, width, mask_h, mask_w, device):
     if len({tuple(t.shape) for t in tabs}) != 1:
         raise RuntimeError(f"place_table_variants: the variants' tables differ in shape: {[tuple(t.shape) for t in tabs]}")
     return torch.stack(tabs).to(device).contiguous()
-
-
-def _check_place_variants(place, masks, nvar, nobj, frames, what):
-    """True when ``place`` / ``masks`` are the per-variant pair (4-D table + 5-D mask stack); a 3-D table with
-    4-D masks is the shared placement (False); a mixed pair is an error"""
-    if place is None or (place.dim() != 4 and masks.dim() != 5):
-        return False
-    _chk(place, "place", torch.int32)
-    nvar = int(nvar)
-    if tuple(place.shape) != (nvar, nobj, frames, 2) or not place.is_contiguous():
-        raise RuntimeError(f"{what}: place must be a contiguous int32 [K = {nvar}, nobj = {nobj}, F = {frames}, 2] table with a "
-                           f"[K, nobj, F, mh, mw] mask stack, got {tuple(place.shape)}")
-    if masks.dim() != 5 or tuple(masks.shape[:3]) != (nvar, nobj, frames) or not masks.is_contiguous():
-        raise RuntimeError(f"{what}: a [K, nobj, F, 2] table needs masks as a contiguous [K = {nvar}, nobj = {nobj}, F = {frames}, "
-                           f"mh, mw] stack, got {tuple(masks.shape)}")
-    return True
 
 
 def _all_or(active, nvar):
@@ -781,38 +788,6 @@ def resample_table_variants(variant_transforms, height, width, mask_h, mask_w, d
     if len(shapes) != 1:
         raise RuntimeError(f"resample_table_variants: the variants' tables differ in shape (objects, frames): {sorted(shapes)}")
     return torch.tensor(rows, dtype=torch.int32).to(device).contiguous()
-
-
-def _check_resample_variants(maps, masks, nvar, nobj, frames, height, width, what):
-    """True when ``maps`` / ``masks`` are the per-variant pair (4-D table + 5-D mask stack); a 3-D table is the
-    shared transform (False; ``_refuse_resample_mix`` has refused a stack next to it); a 4-D table without the stack is an error"""
-    if not torch.is_tensor(maps) or maps.dim() != 4:
-        return False
-    _chk(maps, "resample", torch.int32)
-    nvar = int(nvar)
-    if tuple(maps.shape) != (nvar, nobj, frames, height + width) or not maps.is_contiguous():
-        raise RuntimeError(f"{what}: resample must be a contiguous int32 [K = {nvar}, nobj = {nobj}, F = {frames}, H + W = "
-                           f"{height + width}] table with a [K, nobj, F, mh, mw] mask stack, got {tuple(maps.shape)}")
-    if masks.dim() != 5 or tuple(masks.shape[:3]) != (nvar, nobj, frames) or not masks.is_contiguous():
-        raise RuntimeError(f"{what}: a [K, nobj, F, H + W] resample table needs masks as a contiguous [K = {nvar}, nobj = {nobj}, "
-                           f"F = {frames}, mh, mw] stack, got {tuple(masks.shape)}")
-    return True
-
-
-def _refuse_resample_mix(place, masks, no_background, what, resample=None):
-    if place is not None:
-        raise RuntimeError(f"{what}: resample= and place= are both given: a translation is part of the resample table")
-    if masks.dim() == 5 and not (torch.is_tensor(resample) and resample.dim() == 4):
-        raise RuntimeError(f"{what}: resample= does not take a [K, nobj, F, mh, mw] mask stack: one transform serves all variants")
-    if no_background:
-        raise RuntimeError(f"{what}: resample= with no_background: pass src_map=(nobj, range(nobj)) instead")
-
-
-def _check_resample(maps, nobj, frames, height, width, what):
-    _chk(maps, "resample", torch.int32)
-    if tuple(maps.shape) != (nobj, frames, height + width) or not maps.is_contiguous():
-        raise RuntimeError(f"{what}: resample must be a contiguous int32 [nobj = {nobj}, F = {frames}, H + W = {height + width}] "
-                           f"table, got {tuple(maps.shape)}")
 
 
 def gather_planes(src, maps, out=None):

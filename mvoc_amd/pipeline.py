@@ -26,6 +26,7 @@ from . import ops
 from .latent_cache import LatentCache
 from .pnp_utils import register_time_all
 from .schedulers import DDIMScheduler
+from .unet import PLACEMENT_MODES, frame_shard_refusal
 
 logger = logging.getLogger(__name__)
 H16 = torch.float16
@@ -412,6 +413,12 @@ class CompositionState(dict):
     __slots__ = ("__weakref__",)
 
 
+def _state_mode(st):
+    """the entry of ``PLACEMENT_MODES`` a composition state was made with (``make_composition_state`` sets at most one of the
+    four values), None for a state that places nothing"""
+    return next((m for m in PLACEMENT_MODES if st.get(m.attr) is not None), None)
+
+
 class GraphedStep:
     """Capture one loop iteration (a python callable working on static device buffers) into a hipGraph."""
 
@@ -774,23 +781,27 @@ class I2VGenXLPipeline:
         return tensor2vid(self.conditioner.decode(latents), output_type)
 
     # ---- composition --------------------------------------------------------------------------------------
+    def _move_masks(self, masks, table, mover):
+        """per object the soft and the hard mask moved by ``mover`` (``ops.shift_planes`` / ``ops.gather_planes``, zero fill) with
+        row j of the latent-grid ``table`` -> (masks in the form they came in, the table)"""
+        dev = self.device
+        moved = []
+        for j, (soft, hard) in enumerate(masks):
+            s16 = mover(soft.to(dev, H16).contiguous(), table[j])
+            h16 = mover(hard.to(dev, H16).contiguous(), table[j])
+            moved.append((s16.to(soft.dtype), h16.to(hard.dtype)))
+        return moved, table
+
     def place_masks(self, masks, placement):
         """the call's masks moved to destination coordinates: per object the soft and the hard mask shifted by
         the object's per-frame offsets with zero fill (``ops.shift_planes``) -> (masks in the form they came in, the device
         table int32 [nobj, F, 2] of the latent-grid offsets)"""
         if len(placement) != len(masks):
             raise ValueError(f"placement: offsets for {len(placement)} objects, {len(masks)} masks")
-        dev = self.device
         frames = masks[0][0].shape[-3]
         if any(len(obj) != frames for obj in placement):
             raise ValueError(f"placement: every object needs {frames} per-frame offsets")
-        table = torch.tensor(placement, dtype=torch.int32).to(dev).contiguous()
-        moved = []
-        for j, (soft, hard) in enumerate(masks):
-            s16 = ops.shift_planes(soft.to(dev, H16).contiguous(), table[j])
-            h16 = ops.shift_planes(hard.to(dev, H16).contiguous(), table[j])
-            moved.append((s16.to(soft.dtype), h16.to(hard.dtype)))
-        return moved, table
+        return self._move_masks(masks, torch.tensor(placement, dtype=torch.int32).to(self.device).contiguous(), ops.shift_planes)
 
     def transform_masks(self, masks, transform):
         """the call's masks moved to destination coordinates under a transform: per object the soft and the hard
@@ -799,39 +810,29 @@ class I2VGenXLPipeline:
         int32 [nobj, F, h + w] of those maps)"""
         if len(transform) != len(masks):
             raise ValueError(f"transform: {len(transform)} objects, {len(masks)} masks")
-        dev = self.device
         frames, h, w = masks[0][0].shape[-3:]
         if any(len(t[8]) != frames for t in transform):
             raise ValueError(f"transform: every object needs {frames} per-frame offsets")
-        table = ops.resample_table(transform, h, w, h, w, dev)
-        moved = []
-        for j, (soft, hard) in enumerate(masks):
-            s16 = ops.gather_planes(soft.to(dev, H16).contiguous(), table[j])
-            h16 = ops.gather_planes(hard.to(dev, H16).contiguous(), table[j])
-            moved.append((s16.to(soft.dtype), h16.to(hard.dtype)))
-        return moved, table
+        return self._move_masks(masks, ops.resample_table(transform, h, w, h, w, self.device), ops.gather_planes)
+
+    def _move_variant_masks(self, masks, values, move, tables_key):
+        """the call's masks moved once per variant by ``move`` (``place_masks`` / ``transform_masks``) with each of ``values`` ->
+        dict(``tables_key`` = per variant the device table of its move on the latent grid,
+             masks = (soft, hard) fp16 [K, nobj, F, h, w] stacks for the engine (``unet.variant_masks``),
+             fusion_masks = per variant the soft masks [nobj, 1, 4, F, h, w] fp16 of the fusion steps)"""
+        moved = [move(masks, v) for v in values]
+        first = lambda t: t.reshape(-1, *t.shape[-3:])[0].to(self.device, H16)  # as the engine forms its device masks
+        return {tables_key: [tab for _, tab in moved],
+                "masks": tuple(torch.stack([torch.stack([first(m[i]) for m in mk]) for mk, _ in moved]).contiguous() for i in (0, 1)),
+                "fusion_masks": [torch.stack([m[0].to(self.device, H16) for m in mk]).contiguous() for mk, _ in moved]}
 
     def place_variant_masks(self, masks, variant_placements):
-        """the call's masks moved once per variant (``place_masks`` with each variant's placement) ->
-        dict(place_dev = per variant the device table int32 [nobj, F, 2] of its latent-grid offsets,
-             masks = (soft, hard) fp16 [K, nobj, F, h, w] stacks for the engine (``unet.variant_masks``),
-             fusion_masks = per variant the soft masks [nobj, 1, 4, F, h, w] fp16 of the fusion steps)"""
-        moved = [self.place_masks(masks, pl) for pl in variant_placements]
-        first = lambda t: t.reshape(-1, *t.shape[-3:])[0].to(self.device, H16)  # as the engine forms its device masks
-        return {"place_dev": [tab for _, tab in moved],
-                "masks": tuple(torch.stack([torch.stack([first(m[i]) for m in mk]) for mk, _ in moved]).contiguous() for i in (0, 1)),
-                "fusion_masks": [torch.stack([m[0].to(self.device, H16) for m in mk]).contiguous() for mk, _ in moved]}
+        """``_move_variant_masks`` under per-variant placement: ``place_dev`` = int32 [nobj, F, 2] offsets"""
+        return self._move_variant_masks(masks, variant_placements, self.place_masks, "place_dev")
 
     def transform_variant_masks(self, masks, variant_transforms):
-        """the call's masks gathered once per variant (``transform_masks`` with each variant's transform) ->
-        dict(resample_dev = per variant the device table int32 [nobj, F, h + w] of its latent-grid maps,
-             masks = (soft, hard) fp16 [K, nobj, F, h, w] stacks for the engine (``unet.variant_masks``),
-             fusion_masks = per variant the soft masks [nobj, 1, 4, F, h, w] fp16 of the fusion steps)"""
-        moved = [self.transform_masks(masks, tr) for tr in variant_transforms]
-        first = lambda t: t.reshape(-1, *t.shape[-3:])[0].to(self.device, H16)  # as the engine forms its device masks
-        return {"resample_dev": [tab for _, tab in moved],
-                "masks": tuple(torch.stack([torch.stack([first(m[i]) for m in mk]) for mk, _ in moved]).contiguous() for i in (0, 1)),
-                "fusion_masks": [torch.stack([m[0].to(self.device, H16) for m in mk]).contiguous() for mk, _ in moved]}
+        """``_move_variant_masks`` under per-variant transforms: ``resample_dev`` = int32 [nobj, F, h + w] maps"""
+        return self._move_variant_masks(masks, variant_transforms, self.transform_masks, "resample_dev")
 
     def make_composition_state(self, latents, cond, masks, guidance_scale, dedup_sources=None, variants=1, placement=None,
                                variant_placements=None, transform=None, variant_transforms=None):
@@ -856,46 +857,30 @@ class I2VGenXLPipeline:
         one per variant.  Each variant's masks are gathered once, here; the engine takes them as (soft, hard) [K, nobj, F, h, w]
         stacks, the fusion steps each variant's own.  The hooks keep ``masks`` as they came (shape checks and the mask key)."""
         cond = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in cond.items()}
-        vresample = None
-        if variant_transforms is not None:
-            if placement is not None or variant_placements is not None or transform is not None:
-                raise ValueError("variant_transforms is given together with placement / variant_placements / transform: every "
-                                 "variant's transform carries its own translation, and a call transforms per variant or once")
+        given = {"placement": placement, "variant_placements": variant_placements, "transform": transform,
+                 "variant_transforms": variant_transforms}
+        # the state's keys of the four modes: each mode's value, the shared modes' latent-grid table (place_dev / resample_dev)
+        # and the per-variant modes' ``_move_variant_masks`` dict (vplace / vresample); all None but the active mode's
+        placed = dict.fromkeys(("placement", "place_dev", "variant_placements", "vplace", "transform", "resample_dev",
+                                "variant_transforms", "vresample"))
+        on = [m for m in PLACEMENT_MODES if given[m.attr] is not None]
+        if on:
+            m = on[0]
+            value = given[m.attr]
+            if len(on) > 1:
+                raise ValueError(m.mix.format(set="given"))
             if self.unet.shard is not None:
-                raise RuntimeError("variant_transforms do not combine with the frame shard: the section masks are cut to pixel "
-                                   "slabs and a gather crosses slabs")
-            if len(variant_transforms) != int(variants):
-                raise ValueError(f"variant_transforms: {len(variant_transforms)} transforms for {int(variants)} variants")
-            variant_transforms = tuple(tuple(tr) for tr in variant_transforms)
-            vresample = self.transform_variant_masks(masks, variant_transforms)
-        resample_dev = None
-        if transform is not None:
-            if placement is not None or variant_placements is not None:
-                raise ValueError("transform is given together with placement / variant_placements: a transform carries its own "
-                                 "translation, and one transform serves all variants")
-            if self.unet.shard is not None:
-                raise RuntimeError("a transform does not combine with the frame shard: the section masks are cut to pixel slabs "
-                                   "and a gather crosses slabs")
-            transform = tuple(transform)
-            masks, resample_dev = self.transform_masks(masks, transform)
-        vstate = None
-        if variant_placements is not None:
-            if placement is not None:
-                raise ValueError("variant_placements and placement are both given: a call places its objects per variant or "
-                                 "once for all variants")
-            if self.unet.shard is not None:
-                raise RuntimeError("variant_placements do not combine with the frame shard: the section masks are cut to pixel "
-                                   "slabs and a shift crosses slabs")
-            if len(variant_placements) != int(variants):
-                raise ValueError(f"variant_placements: {len(variant_placements)} placements for {int(variants)} variants")
-            variant_placements = tuple(variant_placements)
-            vstate = self.place_variant_masks(masks, variant_placements)
-        place_dev = None
-        if placement is not None:
-            if self.unet.shard is not None:
-                raise RuntimeError("a placement does not combine with the frame shard: the section masks are cut to pixel slabs "
-                                   "and a shift crosses slabs")
-            masks, place_dev = self.place_masks(masks, placement)
+                raise RuntimeError(frame_shard_refusal(m.subject, m.mover))
+            if m.per_variant and len(value) != int(variants):
+                raise ValueError(f"{m.attr}: {len(value)} {m.items} for {int(variants)} variants")
+            move = self.transform_masks if m.kw == "resample" else self.place_masks
+            if m.per_variant:
+                value = tuple(tuple(v) for v in value)
+                placed["v" + m.kw] = self._move_variant_masks(masks, value, move, m.kw + "_dev")
+            else:
+                value = tuple(value)
+                masks, placed[m.kw + "_dev"] = move(masks, value)
+            placed[m.attr] = value
         n_obj = len(masks)
         nvar = int(variants)
         scales = [float(g) for g in guidance_scale] if isinstance(guidance_scale, (list, tuple)) else [float(guidance_scale)]
@@ -917,10 +902,7 @@ class I2VGenXLPipeline:
               "masks": masks, "variants": {}, "cond": cond, "n_obj": n_obj, "nvar": nvar,
               "fusion_masks": torch.stack([m[0].to(dev, H16) for m in masks]).contiguous(),
               "fusion_objs": torch.empty((n_obj, 1) + tuple(latents.shape[1:]), dtype=H16, device=dev), "maps": {},
-              "placement": placement, "place_dev": place_dev, "place_tables": [],
-              "variant_placements": variant_placements, "vplace": vstate,
-              "transform": transform, "resample_dev": resample_dev,
-              "variant_transforms": variant_transforms, "vresample": vresample})
+              "place_tables": [], **placed})
         weak = weakref.ref(st)  # (the caller holds the state for as long as it steps it)
         st["build_map"] = lambda smap: self._composition_batch(weak(), smap, do_cfg)
         st["maps"][None] = st["build_map"](None)
@@ -964,38 +946,20 @@ class I2VGenXLPipeline:
                 inp[nb - 2 * nvar:nb - nvar].copy_(x)
             inp[nb - nvar:].copy_(x)
             u = self.unet
-            saved, u.prune_source_tail = u.prune_source_tail, bool(self.prune_source_tail)  # this loop reads the destination chunks only
-            saved_pb, u.prune_background = u.prune_background, bool(self.prune_background)  # ... and never the background's output
-            saved_sp, u.shared_prefix_chunks = u.shared_prefix_chunks, (2 if st["share_cfg_prefix"] else 0)
-            saved_sc, u.source_chunks = u.source_chunks, smap
-            saved_nv, u.variants = u.variants, nvar
-            saved_pl, u.placement = u.placement, st["placement"]
-            saved_vp, u.variant_placements = u.variant_placements, st["variant_placements"]
-            vstate = st["vplace"] if st["vplace"] is not None else st["vresample"]
-            saved_vm, u.variant_masks = u.variant_masks, None if vstate is None else vstate["masks"]
-            saved_tr, u.transform = u.transform, st["transform"]
-            saved_vt, u.variant_transforms = u.variant_transforms, st["variant_transforms"]
-            try:
+            mode = _state_mode(st)
+            vstate = st["v" + mode.kw] if mode is not None and mode.per_variant else None
+            with u.scoped(prune_source_tail=bool(self.prune_source_tail),  # this loop reads the destination chunks only
+                          prune_background=bool(self.prune_background),  # ... and never the background's output
+                          shared_prefix_chunks=2 if st["share_cfg_prefix"] else 0, source_chunks=smap, variants=nvar,
+                          placement=st["placement"], variant_placements=st["variant_placements"], transform=st["transform"],
+                          variant_transforms=st["variant_transforms"], variant_masks=None if vstate is None else vstate["masks"]):
                 noise = u.forward_ext(inp, st["t"], mcond["fps"], mcond["image_latents_first"], mcond["image_latents"],
                                       mcond["image_embeddings"], mcond["encoder_hidden_states"], multi_frame_guidance=False,
                                       conditioning=prepared)[0]
-            finally:
-                u.prune_source_tail, u.shared_prefix_chunks, u.source_chunks, u.variants = saved, saved_sp, saved_sc, saved_nv
-                u.placement = saved_pl
-                u.variant_placements, u.variant_masks = saved_vp, saved_vm
-                u.transform = saved_tr
-                u.variant_transforms = saved_vt
-                u.prune_background = saved_pb
-            # the engine's per-level offset tables are read by this state's captured graphs: they live as long as the state,
-            # also after the engine drops its cache for another placement
-            if st["placement"] is not None and not any(d is u._place_cache[1] for d in st["place_tables"]):
-                st["place_tables"].append(u._place_cache[1])
-            if st["variant_placements"] is not None and not any(d is u._vplace_cache[1] for d in st["place_tables"]):
-                st["place_tables"].append(u._vplace_cache[1])
-            if st["transform"] is not None and not any(d is u._resample_cache[1] for d in st["place_tables"]):
-                st["place_tables"].append(u._resample_cache[1])
-            if st["variant_transforms"] is not None and not any(d is u._vresample_cache[1] for d in st["place_tables"]):
-                st["place_tables"].append(u._vresample_cache[1])
+            # the engine's per-level tables of this state's mode are read by its captured graphs: they live as long as the state,
+            # also after the engine drops them for another value of the mode
+            if mode is not None and not any(d is u._level_tables[mode.attr][1] for d in st["place_tables"]):
+                st["place_tables"].append(u._level_tables[mode.attr][1])
             ops.ddim_step(x, noise[nb - nvar:nb].contiguous(), st["coef"],
                           v_uncond=noise[nb - 2 * nvar:nb - nvar].contiguous() if do_cfg else None, out=x)
 
@@ -1004,24 +968,16 @@ class I2VGenXLPipeline:
     def background_dead(self, smap):
         """whether the UNet drops the background chunk on the step the CURRENT hook state describes, run on the batch of source
         map ``smap`` (``unet.background_dead`` as the iteration body will see it: the body sets both attributes)"""
-        u = self.unet
-        saved = u.prune_background, u.source_chunks
-        u.prune_background, u.source_chunks = bool(self.prune_background), smap
-        try:
+        with self.unet.scoped(prune_background=bool(self.prune_background), source_chunks=smap) as u:
             return bool(u.background_dead())
-        finally:
-            u.prune_background, u.source_chunks = saved
 
     def composition_variant_key(self, st, smap):
         """what a captured composition iteration bakes in, as the key of ``st["variants"]`` (see ``composition_step``).  A run
         alternates steps that drop the background chunk and steps that need it: each kind has its own graph"""
-        u = self.unet
+        u, mode = self.unet, _state_mode(st)
         return (u.injection_masks(st["nvar"]), u.mask_key(st["masks"]), bool(u.pair_destinations), bool(u.prune_dead_chunks),
                 bool(self.prune_source_tail), bool(st.get("share_cfg_prefix")), smap, st["nvar"]) + \
-            (() if st["placement"] is None else (st["placement"],)) + \
-            (() if st["variant_placements"] is None else ("variant_placements", st["variant_placements"])) + \
-            (() if st.get("transform") is None else ("transform", st["transform"])) + \
-            (() if st.get("variant_transforms") is None else ("variant_transforms", st["variant_transforms"])) + \
+            (() if mode is None else (mode.attr, st[mode.attr])) + \
             (("no_background",) if self.background_dead(smap) else ())
 
     def composition_step(self, st, t, bg_latents, obj_latents, table_row, fuse=None):
@@ -1030,27 +986,26 @@ class I2VGenXLPipeline:
         one conditioning class) share a chunk: the step's source map picks the batch."""
         if fuse is not None:
             mix, rnf, fobjs = fuse
-            vp = st["vplace"] if st["vplace"] is not None else st.get("vresample")
-            objs16 = [o.to(self.device, H16).contiguous() for o in fobjs] if vp is not None else None
-            for k in range(st["nvar"] if vp is not None else 0):
-                # per-variant placement / transforms: K times nobj launches of the shift (the gather) and one of the
-                # single-variant fusion entry on the variant's slice of the latents -- its object latents moved by ITS offsets
-                # (maps), fused with ITS (moved) masks
-                for j, o in enumerate(objs16):
-                    if st["vplace"] is not None:
-                        ops.shift_planes(o, vp["place_dev"][k][j], out=st["fusion_objs"][j])
+            # the object's inverted latents move with it, by the state's mode: shifted or gathered with the latent-grid table that
+            # moved the fusion masks (zero fill), or copied as they are
+            mode = _state_mode(st)
+            mover = None if mode is None else getattr(ops, mode.mover + "_planes")
+            if mode is not None and mode.per_variant:
+                # K times nobj launches of the shift (the gather) and one of the single-variant fusion entry on the variant's
+                # slice of the latents -- its object latents moved by ITS offsets (maps), fused with ITS (moved) masks
+                vstate = st["v" + mode.kw]
+                objs16 = [o.to(self.device, H16).contiguous() for o in fobjs]
+                for k in range(st["nvar"]):
+                    for j, o in enumerate(objs16):
+                        mover(o, vstate[mode.kw + "_dev"][k][j], out=st["fusion_objs"][j])
+                    lat = st["latents"][k:k + 1]
+                    ops.latent_fusion(lat, bg_latents, st["fusion_objs"], vstate["fusion_masks"][k], mix, rnf, out=lat)
+            else:
+                for j, o in enumerate(fobjs):
+                    if mode is None:
+                        st["fusion_objs"][j].copy_(o)
                     else:
-                        ops.gather_planes(o, vp["resample_dev"][k][j], out=st["fusion_objs"][j])
-                lat = st["latents"][k:k + 1]
-                ops.latent_fusion(lat, bg_latents, st["fusion_objs"], vp["fusion_masks"][k], mix, rnf, out=lat)
-            for j, o in enumerate(fobjs if vp is None else ()):
-                if st.get("resample_dev") is not None:  # ... or is gathered with it (zero fill; the fusion masks are the gathered ones)
-                    ops.gather_planes(o.to(self.device, H16).contiguous(), st["resample_dev"][j], out=st["fusion_objs"][j])
-                elif st["place_dev"] is None:
-                    st["fusion_objs"][j].copy_(o)
-                else:  # the object's inverted latents move with it (zero fill; the fusion masks are the shifted ones)
-                    ops.shift_planes(o.to(self.device, H16).contiguous(), st["place_dev"][j], out=st["fusion_objs"][j])
-            if vp is None:
+                        mover(o.to(self.device, H16).contiguous(), st[mode.kw + "_dev"][j], out=st["fusion_objs"][j])
                 ops.latent_fusion(st["latents"], bg_latents, st["fusion_objs"], st["fusion_masks"], mix, rnf, out=st["latents"],
                                   nvar=st["nvar"])
             obj_latents = fobjs
@@ -1180,18 +1135,11 @@ class I2VGenXLPipeline:
             placement, variant_placements, transform, variant_transforms = resolve_variant_obj_transforms(
                 variant_obj_transforms, nvar, n_obj, num_frames, height // self.vae_scale_factor, width // self.vae_scale_factor,
                 self.vae_scale_factor)
-        if variant_transforms is not None and self.unet.shard is not None:
-            raise RuntimeError("variant_obj_transforms do not combine with the frame shard: the section masks are cut to pixel "
-                               "slabs and a gather crosses slabs")
-        if transform is not None and self.unet.shard is not None:
-            raise RuntimeError("obj_transforms do not combine with the frame shard: the section masks are cut to pixel slabs and a "
-                               "gather crosses slabs")
-        if variant_placements is not None and self.unet.shard is not None:
-            raise RuntimeError("variant_obj_offsets do not combine with the frame shard: the section masks are cut to pixel "
-                               "slabs and a shift crosses slabs")
-        if placement is not None and self.unet.shard is not None:
-            raise RuntimeError("obj_offsets do not combine with the frame shard: the section masks are cut to pixel slabs and a "
-                               "shift crosses slabs")
+        placed = {"placement": placement, "variant_placements": variant_placements, "transform": transform,
+                  "variant_transforms": variant_transforms}  # (at most one is not None: each resolver returns one)
+        for m in PLACEMENT_MODES:
+            if placed[m.attr] is not None and self.unet.shard is not None:
+                raise RuntimeError(frame_shard_refusal(m.arg + " do", m.mover))
         # source de-duplication: roles showing the same image share ONE draw of the VAE posterior (prepare_image_latents samples
         # per role, :860-890) and one vision-tower pass -- else identical frames would give every role its own image latents and
         # no two roles could share a chunk (make_composition_state)
@@ -1274,10 +1222,7 @@ class I2VGenXLPipeline:
             obj_masks_tensors = [mask_preprocess(m, self.device, H16, 1, 4, num_frames, downscale=8) for m in obj_mask]
         self.unet.check_variant_schedules(nvar)  # per-variant injection schedules are hook state (pnp_utils): one entry per variant
         st = self.make_composition_state(latents, cond, obj_masks_tensors, scales if nvar > 1 else guidance_scale, variants=nvar,
-                                         **({} if placement is None else {"placement": placement}),
-                                         **({} if variant_placements is None else {"variant_placements": variant_placements}),
-                                         **({} if transform is None else {"transform": transform}),
-                                         **({} if variant_transforms is None else {"variant_transforms": variant_transforms}))
+                                         **{attr: value for attr, value in placed.items() if value is not None})
         table, index = sched.coef_table(self.device, guidance_scale)
         if nvar > 1:  # [steps, K, 5]: a step's coefficient rows are one view, whatever K is
             table = torch.stack([sched.coef_table(self.device, g)[0] for g in scales], 1).contiguous()

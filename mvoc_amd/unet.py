@@ -21,7 +21,8 @@ Forward entry points follow the reference:
 """
 import math
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
+from contextlib import contextmanager
 
 import torch
 
@@ -616,6 +617,33 @@ class Conditioning:
         return self
 
 
+# The four ways to place objects at composition time (how they are resolved: 6p), highest precedence first:
+# when several are set the first one's ``mix`` sentence is raised.  Per mode: the engine attribute (also the argument and key of the
+# pipeline's composition state), whether it holds one value per variant, the blend keyword its table goes to, the ``ops`` builder
+# of that table, how it moves a plane (``ops.<mover>_planes``), and the words of its messages -- the subject of the frame-shard
+# refusal, the sampling call's argument, what a per-variant value counts, what an object's entry holds, and the mix refusal
+# ("set" on the engine, "given" in the pipeline).
+_Mode = namedtuple("_Mode", "attr per_variant kw builder mover subject arg items holds mix")
+PLACEMENT_MODES = (
+    _Mode("variant_transforms", True, "resample", "resample_table_variants", "gather", "variant_transforms do",
+          "variant_obj_transforms", "transforms", "",
+          "variant_transforms is {set} together with placement / variant_placements / transform: every variant's transform "
+          "carries its own translation, and a call transforms per variant or once"),
+    _Mode("transform", False, "resample", "resample_table", "gather", "a transform does", "obj_transforms", None, "",
+          "transform is {set} together with placement / variant_placements: a transform carries its own translation, and one "
+          "transform serves all variants"),
+    _Mode("variant_placements", True, "place", "place_table_variants", "shift", "variant_placements do",
+          "variant_obj_offsets", "placements", "offsets for ",
+          "variant_placements and placement are both {set}: a call places its objects per variant or once for all variants"),
+    _Mode("placement", False, "place", "place_table", "shift", "a placement does", "obj_offsets", None, "offsets for ", None),
+)
+
+
+def frame_shard_refusal(subject, mover):
+    """why no placement mode runs frame-sharded: ``subject`` = "a placement does", "obj_offsets do", .."""
+    return f"{subject} not combine with the frame shard: the section masks are cut to pixel slabs and a {mover} crosses slabs"
+
+
 class I2VGenXLUNet:
     """MI355X engine with the reference UNet's call protocol."""
 
@@ -681,39 +709,51 @@ class I2VGenXLUNet:
         # paired attention serves the K pairs in one launch.  1 = today's batch, kernels and launches.  Set and restored around
         # its forward by the composition loop, like source_chunks.  Not with a frame shard, not with shared_prefix_chunks.
         self.variants = 1
-        # Placement (pipeline.py obj_offsets): None, or a hashable tuple -- per object, per frame (dy, dx) on the
-        # latent grid (the masks' h x w).  Every injection site then reads object j of frame f at its shifted pixel through the
-        # _placed blend entries (the hook masks are in destination coordinates already: the pipeline shifts them once per call);
-        # the offsets of a site's H x W come from ops.level_offset.  None = today's calls.  Set and restored around its forward
-        # by the composition loop, like source_chunks; shared by the variants.  Not with a frame shard.
+        # Object placement at composition time: four mutually exclusive modes (PLACEMENT_MODES), each None = today's calls.  All four
+        # are set and restored around its forward by the composition loop, like source_chunks, and none combines with a frame
+        # shard or with another of the four: ``_placement_mode`` resolves which is on, and refuses, when a site asks.  The hook
+        # mask lists carry ONE mask set in every mode (shape checks and the mask key).
+        # Placement (pipeline.py obj_offsets): a hashable tuple -- per object, per frame (dy, dx) on the latent grid
+        # (the masks' h x w).  Every injection site then reads object j of frame f at its shifted pixel through the _placed blend
+        # entries (the hook masks are in destination coordinates already: the pipeline shifts them once per call); the offsets
+        # of a site's H x W come from ops.level_offset.  Shared by the variants.
         self.placement = None
-        self._place_cache = (None, {})
-        # Per-variant placement (pipeline.py variant_obj_offsets): None, or a hashable tuple of K = ``variants``
-        # placements in the format of ``placement`` (a variant that is not placed carries all-zero offsets).  Every injection site
-        # then passes ``variant_masks`` -- (soft, hard) fp16 stacks [K, nobj, F, h, w] on the device, variant k's masks in ITS
-        # destination coordinates -- and the per-level [K, nobj, F, 2] table to the _placed_variants blend entries.  The hook mask
-        # lists still carry ONE mask set (shape checks and the mask key).  Set and restored around its forward by the composition
-        # loop, like placement; not together with placement, not with a frame shard.
+        # Per-variant placement (pipeline.py variant_obj_offsets): a hashable tuple of K = ``variants`` placements
+        # in the format of ``placement`` (a variant that is not placed carries all-zero offsets).  Every injection site then
+        # passes ``variant_masks`` -- (soft, hard) fp16 stacks [K, nobj, F, h, w] on the device, variant k's masks in ITS
+        # destination coordinates -- and the per-level [K, nobj, F, 2] table to the _placed_variants blend entries.
         self.variant_placements = None
         self.variant_masks = None
-        self._vplace_cache = (None, {})
-        # Scale and mirror (pipeline.py obj_transforms): None, or a hashable tuple -- per object (py, qy, px, qx,
-        # flip_y, flip_x, ay2, ax2, ((dy, dx) per frame)): scale p / q per axis, mirror flags, twice the anchor and the per-frame
+        # Scale and mirror (pipeline.py obj_transforms): a hashable tuple -- per object (py, qy, px, qx, flip_y,
+        # flip_x, ay2, ax2, ((dy, dx) per frame)): scale p / q per axis, mirror flags, twice the anchor and the per-frame
         # translation, all on the latent grid.  Every injection site then reads object j of frame f at the pixel its per-axis maps
         # name (ops.level_axis_map for the site's H x W) through the _resampled blend entries; the hook masks are in destination
-        # coordinates already (the pipeline gathers them once per call).  None = today's calls.  Set and restored around its forward
-        # by the composition loop, like placement; shared by the variants.  Not with placement / variant_placements, not with a
-        # frame shard.
+        # coordinates already (the pipeline gathers them once per call).  Shared by the variants.
         self.transform = None
-        self._resample_cache = (None, {})
-        # Per-variant transforms (pipeline.py variant_obj_transforms): None, or a hashable tuple of K = ``variants``
+        # Per-variant transforms (pipeline.py variant_obj_transforms): a hashable tuple of K = ``variants``
         # transforms in the format of ``transform`` (a variant that is not transformed carries the identity: scale 1/1, no flip,
         # anchor at the frame centre, zero offsets).  Every injection site then passes ``variant_masks`` -- variant k's masks
-        # gathered with ITS maps -- and the per-level [K, nobj, F, H + W] table to the _resampled_variants blend entries.  Set and
-        # restored around its forward by the composition loop, like variant_placements; not together with placement /
-        # variant_placements / transform, not with a frame shard.
+        # gathered with ITS maps -- and the per-level [K, nobj, F, H + W] table to the _resampled_variants blend entries.
         self.variant_transforms = None
-        self._vresample_cache = (None, {})
+        # the modes' device tables: attribute name -> (value, {(H, W, mh, mw): table}); a mode's tables are dropped when ITS value
+        # changes, so states of different modes that step alternately keep theirs
+        self._level_tables = {m.attr: (None, {}) for m in PLACEMENT_MODES}
+
+    @contextmanager
+    def scoped(self, **attrs):
+        """set the given engine attributes for the ``with`` body and put their earlier values back afterwards, also when the
+        body raises.  A name the engine does not have is refused: a misspelt keyword must not create an attribute"""
+        for name in attrs:
+            if name not in self.__dict__:
+                raise AttributeError(f"scoped: the engine has no attribute {name!r}")
+        saved = {name: getattr(self, name) for name in attrs}
+        try:
+            for name, value in attrs.items():
+                setattr(self, name, value)
+            yield self
+        finally:
+            for name, value in saved.items():
+                setattr(self, name, value)
 
     def set_frame_shard(self, shard):
         """Frame-shard every forward over the ranks of ``shard`` (``mvoc_amd.frame_shard``): each rank receives the FULL
@@ -904,63 +944,62 @@ class I2VGenXLUNet:
             return None
         return nsrc, chunks
 
-    def place_table(self, mask_list, H, W):
-        """the ``place=`` argument of a site's blend at H x W: None without a placement, else the device table of per-(object,
-        frame) feature offsets, cached per (placement, H, W) and dropped when the placement changes"""
-        if self.variant_placements is not None:
-            return self.variant_place_table(mask_list, H, W)
-        pl = self.placement
-        if pl is None:
+    def _placement_mode(self, mask_list=None):
+        """the one place that reads the four placement attributes: None when no object is placed, else the active entry of
+        ``PLACEMENT_MODES``.  Refused here, in this order: two modes at once (the message of the one that comes first in
+        PLACEMENT_MODES), a frame shard and -- given the hooks' ``mask_list`` -- a value that does not hold one entry per variant
+        and, in each, one per object"""
+        on = [m for m in PLACEMENT_MODES if getattr(self, m.attr) is not None]
+        if not on:
             return None
+        m = on[0]
+        if len(on) > 1:
+            raise RuntimeError(m.mix.format(set="set"))
         if self.shard is not None:
-            raise RuntimeError("a placement does not combine with the frame shard: the section masks are cut to pixel slabs "
-                               "and a shift crosses slabs")
-        if len(pl) != len(mask_list):
-            raise RuntimeError(f"placement holds offsets for {len(pl)} objects, the hooks carry {len(mask_list)} masks")
-        if self._place_cache[0] != pl:
-            self._place_cache = (pl, {})
-        mh, mw = self._all_frame_masks(mask_list)[0].shape[2:]
-        key = (H, W, mh, mw)
-        tab = self._place_cache[1].get(key)
-        if tab is None:
-            tab = self._place_cache[1][key] = ops.place_table(pl, H, W, mh, mw, self.device)
-        return tab
+            raise RuntimeError(frame_shard_refusal(m.subject, m.mover))
+        if mask_list is not None:
+            value = getattr(self, m.attr)
+            if m.per_variant and len(value) != self.variants:
+                raise RuntimeError(f"{m.attr} holds {len(value)} {m.items}, the call {self.variants} variants")
+            for k, v in enumerate(value if m.per_variant else (value,)):
+                if len(v) != len(mask_list):
+                    raise RuntimeError(f"{m.attr}{f'[{k}]' if m.per_variant else ''} holds {m.holds}{len(v)} objects, the hooks carry "
+                                       f"{len(mask_list)} masks")
+        return m
 
-    def variant_place_table(self, mask_list, H, W):
-        """the ``place=`` argument under ``variant_placements``: the device table [K, nobj, F, 2] of this H x W, cached per
-        (variant_placements, H, W, mh, mw) and dropped when the placements change"""
-        vp = self.variant_placements
-        if self.placement is not None:
-            raise RuntimeError("variant_placements and placement are both set: a call places its objects per variant or once "
-                               "for all variants")
-        if self.shard is not None:
-            raise RuntimeError("variant_placements do not combine with the frame shard: the section masks are cut to pixel "
-                               "slabs and a shift crosses slabs")
-        if len(vp) != self.variants:
-            raise RuntimeError(f"variant_placements holds {len(vp)} placements, the call {self.variants} variants")
-        for k, pl in enumerate(vp):
-            if len(pl) != len(mask_list):
-                raise RuntimeError(f"variant_placements[{k}] holds offsets for {len(pl)} objects, the hooks carry "
-                                   f"{len(mask_list)} masks")
-        if self._vplace_cache[0] != vp:
-            self._vplace_cache = (vp, {})
+    def place_kw(self, mask_list, H, W):
+        """keyword arguments of a site's blend call: none without a placement or transform (exactly today's call), else
+        ``place=`` -- or, under ``transform`` / ``variant_transforms``, ``resample=`` -- the level's device table: [nobj, F, 2]
+        offsets or [nobj, F, H + W] per-axis index maps, with a leading K in the per-variant modes.  Built once per (value, H, W,
+        mh, mw) and dropped when the mode's value changes"""
+        m = self._placement_mode(mask_list)
+        if m is None:
+            return {}
+        value = getattr(self, m.attr)
+        if self._level_tables[m.attr][0] != value:
+            self._level_tables[m.attr] = (value, {})
+        tables = self._level_tables[m.attr][1]
         mh, mw = self._all_frame_masks(mask_list)[0].shape[2:]
         key = (H, W, mh, mw)
-        tab = self._vplace_cache[1].get(key)
-        if tab is None:
-            tab = self._vplace_cache[1][key] = ops.place_table_variants(vp, H, W, mh, mw, self.device)
-        return tab
+        if key not in tables:
+            tables[key] = getattr(ops, m.builder)(value, H, W, mh, mw, self.device)
+        return {m.kw: tables[key]}
+
+    def place_table(self, mask_list, H, W):
+        """the ``place=`` argument of a site's blend at H x W: None without a placement (or under a transform), else the table
+        of ``place_kw``"""
+        return self.place_kw(mask_list, H, W).get("place")
 
     def site_masks(self, masks, kind):
         """the masks a site's blend reads (kind 0 = soft, 1 = hard): ``masks`` [nobj, F, h, w] of the hook state, or under
         ``variant_placements`` / ``variant_transforms`` the [K, nobj, F, h, w] stack of ``variant_masks`` (checked against the
         hook masks' shape)"""
-        if self.variant_placements is None and self.variant_transforms is None:
+        m = self._placement_mode()
+        if m is None or not m.per_variant:
             return masks
         vm = self.variant_masks
         if vm is None:
-            which = "variant_placements" if self.variant_placements is not None else "variant_transforms"
-            raise RuntimeError(f"{which} is set but variant_masks is not: the engine needs the (soft, hard) "
+            raise RuntimeError(f"{m.attr} is set but variant_masks is not: the engine needs the (soft, hard) "
                                "[K, nobj, F, h, w] mask stacks of the placed variants")
         stack = vm[kind]
         if stack.dim() != 5 or stack.shape[0] != self.variants or tuple(stack.shape[1:]) != tuple(masks.shape):
@@ -968,75 +1007,9 @@ class I2VGenXLUNet:
                                f"{', '.join(str(n) for n in masks.shape)}] (the hook masks per variant)")
         return stack
 
-    def resample_table(self, mask_list, H, W):
-        """the ``resample=`` argument of a site's blend at H x W under ``transform``: the device table [nobj, F, H + W] of per-axis
-        index maps, cached per (transform, H, W, mh, mw) and dropped when the transform changes"""
-        tr = self.transform
-        if self.placement is not None or self.variant_placements is not None:
-            raise RuntimeError("transform is set together with placement / variant_placements: a transform carries its own "
-                               "translation, and one transform serves all variants")
-        if self.shard is not None:
-            raise RuntimeError("a transform does not combine with the frame shard: the section masks are cut to pixel slabs "
-                               "and a gather crosses slabs")
-        if len(tr) != len(mask_list):
-            raise RuntimeError(f"transform holds {len(tr)} objects, the hooks carry {len(mask_list)} masks")
-        if self._resample_cache[0] != tr:
-            self._resample_cache = (tr, {})
-        mh, mw = self._all_frame_masks(mask_list)[0].shape[2:]
-        key = (H, W, mh, mw)
-        tab = self._resample_cache[1].get(key)
-        if tab is None:
-            tab = self._resample_cache[1][key] = ops.resample_table(tr, H, W, mh, mw, self.device)
-        return tab
-
-    def variant_resample_table(self, mask_list, H, W):
-        """the ``resample=`` argument under ``variant_transforms``: the device table [K, nobj, F, H + W] of this H x W, cached per
-        (variant_transforms, H, W, mh, mw) and dropped when the transforms change"""
-        vt = self.variant_transforms
-        if self.placement is not None or self.variant_placements is not None or self.transform is not None:
-            raise RuntimeError("variant_transforms is set together with placement / variant_placements / transform: every "
-                               "variant's transform carries its own translation, and a call transforms per variant or once")
-        if self.shard is not None:
-            raise RuntimeError("variant_transforms do not combine with the frame shard: the section masks are cut to pixel "
-                               "slabs and a gather crosses slabs")
-        if len(vt) != self.variants:
-            raise RuntimeError(f"variant_transforms holds {len(vt)} transforms, the call {self.variants} variants")
-        for k, tr in enumerate(vt):
-            if len(tr) != len(mask_list):
-                raise RuntimeError(f"variant_transforms[{k}] holds {len(tr)} objects, the hooks carry {len(mask_list)} masks")
-        if self._vresample_cache[0] != vt:
-            self._vresample_cache = (vt, {})
-        mh, mw = self._all_frame_masks(mask_list)[0].shape[2:]
-        key = (H, W, mh, mw)
-        tab = self._vresample_cache[1].get(key)
-        if tab is None:
-            tab = self._vresample_cache[1][key] = ops.resample_table_variants(vt, H, W, mh, mw, self.device)
-        return tab
-
-    def place_kw(self, mask_list, H, W):
-        """keyword arguments of a site's blend call: none without a placement or transform (exactly today's call), else
-        ``place=`` -- or, under ``transform`` / ``variant_transforms``, ``resample=`` the level's table"""
-        if self.variant_transforms is not None:
-            return {"resample": self.variant_resample_table(mask_list, H, W)}
-        if self.transform is not None:
-            return {"resample": self.resample_table(mask_list, H, W)}
-        tab = self.place_table(mask_list, H, W)
-        return {} if tab is None else {"place": tab}
-
     def pnp_batch(self, B, mask_list):
         """(ndst, source map) of an injection site's batch of B chunks (``check_pnp_batch`` under ``source_chunks``)"""
-        if self.transform is not None and self.shard is not None:
-            raise RuntimeError("a transform does not combine with the frame shard: the section masks are cut to pixel slabs "
-                               "and a gather crosses slabs")
-        if self.variant_transforms is not None and self.shard is not None:
-            raise RuntimeError("variant_transforms do not combine with the frame shard: the section masks are cut to pixel "
-                               "slabs and a gather crosses slabs")
-        if self.placement is not None and self.shard is not None:
-            raise RuntimeError("a placement does not combine with the frame shard: the section masks are cut to pixel slabs "
-                               "and a shift crosses slabs")
-        if self.variant_placements is not None and self.shard is not None:
-            raise RuntimeError("variant_placements do not combine with the frame shard: the section masks are cut to pixel "
-                               "slabs and a shift crosses slabs")
+        placed = self._placement_mode() is not None  # (refuses a placement mode under a frame shard)
         smap = self.pnp_src_map()
         if smap is not None and len(smap[1]) != len(mask_list):
             raise RuntimeError(f"source_chunks maps {len(smap[1])} objects, the hooks carry {len(mask_list)} masks")
@@ -1052,8 +1025,7 @@ class I2VGenXLUNet:
             nsrc = (len(mask_list) if smap is None else smap[0] - 1)
             chunks = tuple(range(nsrc)) if smap is None else tuple(c - 1 for c in smap[1])
             ndst = self.check_pnp_batch(B, mask_list, nsrc, self.variants, no_background=True)
-            positional = smap is None and self.variants == 1 and self.placement is None and self.variant_placements is None \
-                and self.transform is None and self.variant_transforms is None
+            positional = smap is None and self.variants == 1 and not placed
             return ndst, (None if positional else (nsrc, chunks))
         return self.check_pnp_batch(B, mask_list, None if smap is None else smap[0], self.variants), smap
 

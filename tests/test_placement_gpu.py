@@ -514,7 +514,7 @@ def test_unet_placed_forward_equals_the_preshifted_unplaced_forward(kind):
         assert c[3] == [list(map(list, o)) for o in ops.level_offsets(placement, c[1], c[2], h, w)], c
     assert torch.equal(_i16(got[3:]), _i16(ref[3:])), kind
     assert torch.isfinite(got[3:]).all() and not torch.equal(got[3:], plain[3:]), kind  # the placement moved something
-    assert eng.placement is None and len(eng._place_cache[1]) == len({c[1:3] for c in pre.calls})
+    assert eng.placement is None and len(eng._level_tables["placement"][1]) == len({c[1:3] for c in pre.calls})
 
 
 def test_unet_with_a_frame_shard_refuses_a_placement():

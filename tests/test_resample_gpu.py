@@ -587,7 +587,7 @@ def test_unet_transformed_forward_equals_the_pregathered_unplaced_forward(kind):
         assert c[3] == ops.transform_maps(tr, c[1], c[2], h, w), c[:3]
     assert torch.equal(_i16(got[3:]), _i16(ref[3:])), kind
     assert torch.isfinite(got[3:]).all() and not torch.equal(got[3:], plain[3:]), kind  # the transform moved something
-    assert eng.transform is None and len(eng._resample_cache[1]) == len({c[1:3] for c in pre.calls})
+    assert eng.transform is None and len(eng._level_tables["transform"][1]) == len({c[1:3] for c in pre.calls})
 
 
 def test_unet_refuses_a_transform_with_a_shard_a_placement_or_a_wrong_object_count():

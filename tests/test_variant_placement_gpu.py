@@ -400,7 +400,7 @@ def test_unet_variant_placements_equal_the_single_variant_placed_forwards(kind):
         pnp_utils.register_time_all(pipe, t, masks)  # the hooks carry ONE mask set: the call's, as it came
         names = src + [f"u{k}" for k in range(K)] + [f"c{k}" for k in range(K)]
         got = forward(names, variants=K, variant_placements=vp, variant_masks=vstate["masks"])
-        tables = dict(eng._vplace_cache[1])
+        tables = dict(eng._level_tables["variant_placements"][1])
         plain = forward(names, variants=K)
         refs = []
         for k, pl in enumerate(vp):

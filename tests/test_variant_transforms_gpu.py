@@ -490,7 +490,7 @@ def test_unet_variant_transforms_equal_the_single_variant_transformed_forwards(k
         pnp_utils.register_time_all(pipe, t, masks)  # the hooks carry ONE mask set: the call's, as it came
         names = src + [f"u{k}" for k in range(K)] + [f"c{k}" for k in range(K)]
         got = forward(names, variants=K, variant_transforms=vt, variant_masks=vstate["masks"])
-        tables = dict(eng._vresample_cache[1])
+        tables = dict(eng._level_tables["variant_transforms"][1])
         plain = forward(names, variants=K)
         refs = []
         for k, tr in enumerate(vt):
