@@ -13,8 +13,8 @@ thresholds of its own.  An entry's ``obj_offset: [[dx, dy], ...]`` (one item per
 pixels in multiples of 8) places the objects at composition time (``placement_kwargs``; shared by the entry's variants).
 A variant's ``placement: [[dx, dy], ...]`` (the format of ``obj_offset``) places the objects for that variant alone
 (``variant_placement_kwargs``); a variant without the key takes the entry's ``obj_offset``, or none.
-An entry's ``obj_transform: [{offset, scale, flip, anchor}, ...]`` (one dict per object, every key optional) scales, mirrors and
-places the objects at composition time (``transform_kwargs``; shared by the entry's variants, not with ``obj_offset`` or a
+An entry's ``obj_transform: [{offset, scale, flip, anchor, rotate}, ...]`` (one dict per object, every key optional) scales,
+mirrors, turns (``rotate``: degrees counter-clockwise or one angle per frame, not in a variant's ``transform``) and places the objects at composition time (``transform_kwargs``; shared by the entry's variants, not with ``obj_offset`` or a
 variant's ``placement``).  A variant's ``transform: [{...}, ...]`` (the format of ``obj_transform``) transforms the objects for
 that variant alone; a variant without the key takes the entry's ``obj_transform``, or none.
 """
@@ -161,7 +161,7 @@ def variant_placement_kwargs(config, variants):
 
 
 def transform_kwargs(config, variants=None):
-    """the entry's optional ``obj_transform`` (one dict per object: ``offset``, ``scale``, ``flip``, ``anchor``)
+    """the entry's optional ``obj_transform`` (one dict per object: ``offset``, ``scale``, ``flip``, ``anchor``, ``rotate``)
     with the placements of ``variant_placement_kwargs``: none of the keys -> {} (exactly today's call); ``obj_transform`` alone
     -> ``obj_transforms`` as plain dicts and lists (the call checks and normalises them; shared by the entry's variants: not one
     of ``VARIANT_KEYS``); together with ``obj_offset`` or any variant's ``placement`` it is an error -- a transform carries its

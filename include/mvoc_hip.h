@@ -468,6 +468,31 @@ int mvoc_pnp_blend_scatter_nchw_resampled_variants(const mvoc_pnp_desc* d, int32
  * of one call belong to one object, as for mvoc_shift_planes_f16).  Every int32 entry is valid (compared unsigned). */
 int mvoc_gather_planes_f16(const void* src, void* dst, int32_t nplane, int32_t frames, int32_t h, int32_t w,
                            const int32_t* maps, void* stream);
+/* Rotation: the _resampled entries with ONE 2-D index map in place of the two per-axis maps -- a rotation is not
+ * separable.  `map` is a DEVICE table of int32 [nobj][frames][height * width] for THIS call's height x width: entry
+ * (j * frames + f) * height * width + py * width + px is the linear source pixel sy * width + sx that object j of frame f
+ * contributes to destination pixel (py, px); the caller owns the table and keeps it unchanged for as long as a captured graph may
+ * replay the launch.  The object is present iff (uint32_t)entry < height * width -- -1 by convention, but EVERY int32 value is
+ * safe: one unsigned compare takes the negative and the too-large entries alike.  Absent: value 0 and mask 0 enter the same
+ * three fp16-rounded ops (nothing is skipped).  Masks (DESTINATION coordinates, mvoc_gather_planes_warped_f16 moves them there),
+ * object order, ndst, base_chunk0, the source map, nvar and `active` are those of _resampled.  The destination rows are
+ * bit-identical to the unplaced entries on object chunks gathered through the map with zero fill and masks zeroed where an entry
+ * is outside; a map ymap[py] * width + xmap[px] (-1 where either is outside) is the _resampled entry with those per-axis maps.
+ * The nchw entry reads the object values one pixel at a time; the base and the destinations are 16-byte vectors when
+ * height * width is a multiple of 8 and x / x2 are 16-byte aligned.  Bytes counted per launch (MvocProfScope): those of _placed
+ * + 4 * nobj*frames*height*width for the table.  The table's contents are on the device and are not read by the host.
+ * Requires a non-NULL table, 1 <= nvar <= 8, 1 <= active < (1u << nvar), a valid source map and base_chunk0 != -1 (else -1 and an
+ * error text, nothing written); height * width < 2^31 and, for tokens, the alignment rules of every tokens entry (else -2). */
+int mvoc_pnp_blend_scatter_tokens_warped(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
+                                         uint32_t active, const int32_t* map, void* stream);
+int mvoc_pnp_blend_scatter_nchw_warped(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
+                                       uint32_t active, const int32_t* map, void* stream);
+/* Zero-filled per-frame gather of contiguous fp16 planes [nplane][frames][h][w] through a 2-D map (src != dst):
+ *     dst[pl][f][y][x] = src[pl][f] at the linear pixel map_f[y * w + x], or 0 where that entry lies outside [0, h * w)
+ * `map`: DEVICE int32 [frames][h * w], shared by the nplane planes (the planes of one call belong to one object, as for
+ * mvoc_shift_planes_f16).  Every int32 entry is valid (compared unsigned).  Refuses what mvoc_gather_planes_f16 refuses. */
+int mvoc_gather_planes_warped_f16(const void* src, void* dst, int32_t nplane, int32_t frames, int32_t h, int32_t w,
+                                  const int32_t* map, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Loop glue on [B,4,F,h,w] fp16 latents, BIT-EXACT vs the reference's eager fp16 op chain.

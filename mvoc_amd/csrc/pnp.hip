@@ -111,36 +111,12 @@ __global__ __launch_bounds__(256) void pnp_nchw_kernel(const PnpArgs p) {
 //   variant scatter blend_scatter: objects loaded ONCE and kept in registers across the variant loop; one blend for every
 //                   variant when the base is chunk 0, else per variant on its own cond chunk; ndst stores per variant; SEL =
 //                   bit k of `active` clear: variant k's chunks are neither read nor written (wave-uniform, a kernel argument)
+// blend_scatter is in pnp_blend.h (pnp_warp.hip composes its MAP2 kernels from it as well);
 // blend_scatter_per_variant (pnp_blend.h) is the same pieces with the object load INSIDE the variant loop.
 //   _variants = <DIRECT, no SEL>   _variants_sel = <DIRECT, SEL>   _placed = <SHIFT, SEL>   _resampled = <MAP, SEL>
 //   _placed_variants = per-variant <SHIFT, SEL>   (_resampled_variants = per-variant <MAP, SEL>: pnp_variants2.hip)
 // NOBJ is a template parameter, so the object arrays are indexed by unrolled constants only (a run-time-indexed array would go
 // to scratch, see PnpArgs.obj_map).
-template <class L, Src S, bool SEL, int NOBJ>
-__device__ __forceinline__ void blend_scatter(const PnpArgs& p, int nvar, unsigned active, const int* __restrict__ tab) {
-  L it;
-  if (!it.init(p)) return;
-  half_t* x = p.x[blockIdx.y];
-  Objs<S, NOBJ, L::W, L::NM> o;
-  it.template load<S, NOBJ>(p, x, p.masks, tab, o);
-  half_t t[L::W];
-  if (p.base_chunk0) {  // one blend for every injecting variant
-    ld_vec<L::W>(t, x + it.off);
-    blend(t, o, t);
-  }
-  for (int k = 0; k < nvar; ++k) {
-    if constexpr (SEL)
-      if (!((active >> k) & 1u)) continue;
-    half_t* cond = x + var_dst(p, nvar, p.ndst - 1, k) * it.chunk + it.off;
-    if (!p.base_chunk0) {
-      ld_vec<L::W>(t, cond);
-      blend(t, o, t);
-    }
-    if (p.ndst == 2) st_vec<L::W>(x + var_dst(p, nvar, 0, k) * it.chunk + it.off, t);
-    st_vec<L::W>(cond, t);
-  }
-}
-
 template <int NOBJ>
 __global__ __launch_bounds__(256) void pnp_tokens_variants_kernel(const PnpArgs p, const int nvar) {
   blend_scatter<Tokens, DIRECT, false, NOBJ>(p, nvar, 0u, nullptr);

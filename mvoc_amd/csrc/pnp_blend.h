@@ -1,7 +1,8 @@
 // The pieces of the blend-scatter family that more than one translation unit composes its kernels
 // from: the argument block and what fills / refuses it, the fp16 blend, the two item geometries with their object loads, the
 // per-variant scatter and the host launch path.  pnp.hip holds the family's ten kernels (and the text that describes the
-// pieces); pnp_variants2.hip the per-variant MAP form.  Everything is in an anonymous namespace: each unit gets its own copy.
+// pieces); pnp_variants2.hip the per-variant MAP form; pnp_warp.hip the MAP2 form (a 2-D index map: rotation).
+// Everything is in an anonymous namespace: each unit gets its own copy.
 #pragma once
 #include <type_traits>
 
@@ -95,13 +96,24 @@ __device__ __forceinline__ bool resampled_src(const int* __restrict__ maps, int 
   return sy < (unsigned)h && sx < (unsigned)w;
 }
 
-enum Src { DIRECT, SHIFT, MAP };
+// MAP2: map = int32 [nobj][frames][height * width], the linear source pixel sy * width + sx of every destination pixel -- a device
+// table for THIS site's H x W, constant for the whole call (a rotation is not separable into per-axis maps).  One
+// UNSIGNED compare against height * width takes the negative and the too-large entries alike: every int32 entry is safe.
+__device__ __forceinline__ bool warped_src(const int* __restrict__ map, int j, int frames, int f, int py, int px, int h, int w,
+                                           long& spix) {
+  const unsigned s = (unsigned)map[((long)j * frames + f) * h * w + py * w + px];
+  spix = (long)s;
+  return s < (unsigned)(h * w);
+}
+
+enum Src { DIRECT, SHIFT, MAP, MAP2 };
 
 template <Src S>
 __device__ __forceinline__ bool obj_src(const int* __restrict__ tab, int j, int frames, int f, int py, int px, int h, int w,
                                         long& spix) {
   if constexpr (S == SHIFT) return placed_src(tab, j, frames, f, py, px, h, w, spix);
-  else return resampled_src(tab, j, frames, f, py, px, h, w, spix);
+  else if constexpr (S == MAP) return resampled_src(tab, j, frames, f, py, px, h, w, spix);
+  else return warped_src(tab, j, frames, f, py, px, h, w, spix);
 }
 
 // NOBJ object vectors of W elements with NM mask values each (tokens: one pixel, NM = 1; NCHW: one per pixel)
@@ -267,6 +279,32 @@ struct Nchw {
     }
   }
 };
+
+// The variant scatter with the objects loaded ONCE (pnp.hip has the text on the pieces and the kernels made of them)
+template <class L, Src S, bool SEL, int NOBJ>
+__device__ __forceinline__ void blend_scatter(const PnpArgs& p, int nvar, unsigned active, const int* __restrict__ tab) {
+  L it;
+  if (!it.init(p)) return;
+  half_t* x = p.x[blockIdx.y];
+  Objs<S, NOBJ, L::W, L::NM> o;
+  it.template load<S, NOBJ>(p, x, p.masks, tab, o);
+  half_t t[L::W];
+  if (p.base_chunk0) {  // one blend for every injecting variant
+    ld_vec<L::W>(t, x + it.off);
+    blend(t, o, t);
+  }
+  for (int k = 0; k < nvar; ++k) {
+    if constexpr (SEL)
+      if (!((active >> k) & 1u)) continue;
+    half_t* cond = x + var_dst(p, nvar, p.ndst - 1, k) * it.chunk + it.off;
+    if (!p.base_chunk0) {
+      ld_vec<L::W>(t, cond);
+      blend(t, o, t);
+    }
+    if (p.ndst == 2) st_vec<L::W>(x + var_dst(p, nvar, 0, k) * it.chunk + it.off, t);
+    st_vec<L::W>(cond, t);
+  }
+}
 
 // A table and masks PER VARIANT: masks are [nvar][nobj][frames][mask_h][mask_w] (variant k's masks in ITS destination
 // coordinates), the table is [nvar][nobj][frames][2] (S = SHIFT: offsets) or [nvar][nobj][frames][height + width]

@@ -549,11 +549,21 @@ def _active_mask(active, nvar, what):
     return None if active == (1 << nvar) - 1 else active
 
 
-def _blend_entry(what, place, resample, mask_dim, no_background, src_map, nvar, active):
+def _blend_entry(what, place, resample, mask_dim, no_background, src_map, nvar, active, warp=None):
     """the suffix of the library entry mvoc_pnp_blend_scatter_<layout><suffix> that the arguments of ``pnp_blend_<layout>``
     select, by the form of ``place`` / ``resample`` (None, a 3-D table shared by the variants, a 4-D table per variant) and of the
-    masks (4-D, or a 5-D [K, nobj, F, mh, mw] stack, which goes with a 4-D table only); every other combination is refused"""
+    masks (4-D, or a 5-D [K, nobj, F, mh, mw] stack, which goes with a 4-D table only), or by ``warp`` (a 3-D table shared by the
+    variants); every other combination is refused"""
     dim = lambda t: t.dim() if torch.is_tensor(t) else None
+    if warp is not None:
+        if place is not None or resample is not None:
+            raise RuntimeError(f"{what}: warp= is given together with place= / resample=: the 2-D map carries scale, mirror and "
+                               "translation")
+        if mask_dim == 5:
+            raise RuntimeError(f"{what}: warp= does not take a [K, nobj, F, mh, mw] mask stack: one warp serves all variants")
+        if no_background:
+            raise RuntimeError(f"{what}: warp= with no_background: pass src_map=(nobj, range(nobj)) instead")
+        return "_warped"
     if resample is not None:
         if place is not None:
             raise RuntimeError(f"{what}: resample= and place= are both given: a translation is part of the resample table")
@@ -572,9 +582,16 @@ def _blend_entry(what, place, resample, mask_dim, no_background, src_map, nvar, 
 
 
 def _check_table(what, name, table, masks, nvar, d):
-    """the form of a ``place`` ([.., 2]) or ``resample`` ([.., H + W]) table against the descriptor: int32 [nobj, F, ..], or per
-    variant [K, nobj, F, ..] next to a [K, nobj, F, mh, mw] mask stack"""
+    """the form of a ``place`` ([.., 2]), ``resample`` ([.., H + W]) or ``warp`` ([nobj, F, H * W], never per variant) table
+    against the descriptor: int32 [nobj, F, ..], or per variant [K, nobj, F, ..] next to a [K, nobj, F, mh, mw]
+    mask stack"""
     _chk(table, name, torch.int32)
+    if name == "warp":
+        shape = (d.nobj, d.frames, d.height * d.width)
+        if tuple(table.shape) != shape or not table.is_contiguous():
+            raise RuntimeError(f"{what}: warp must be a contiguous int32 [nobj = {d.nobj}, F = {d.frames}, H * W = {shape[2]}] "
+                               f"table, got {tuple(table.shape)}")
+        return
     last, size = ("2", 2) if name == "place" else ("H + W", d.height + d.width)
     shape, dims = (d.nobj, d.frames, size), f"nobj = {d.nobj}, F = {d.frames}"
     if table.dim() == 4:
@@ -587,12 +604,12 @@ def _check_table(what, name, table, masks, nvar, d):
                            f"contiguous [{dims}, mh, mw] stack, got {tuple(masks.shape)}")
 
 
-def _pnp_blend(layout, d, x, x2, masks, need, ndst, src_map, nvar, active, place, resample, no_background=False):
+def _pnp_blend(layout, d, x, x2, masks, need, ndst, src_map, nvar, active, place, resample, no_background=False, warp=None):
     """call the library entry mvoc_pnp_blend_scatter_<layout><suffix> that the arguments of ``pnp_blend_<layout>`` select
     (``_blend_entry``) on the descriptor ``d``; ``need(nchunk)``: elements a tensor must hold from its first for a batch of
     nchunk chunks"""
     what = f"pnp_blend_{layout}"
-    suffix = _blend_entry(what, place, resample, masks.dim(), no_background, src_map, nvar, active)
+    suffix = _blend_entry(what, place, resample, masks.dim(), no_background, src_map, nvar, active, warp)
 
     def call(*args):
         name = f"pnp_blend_scatter_{layout}{suffix}"
@@ -608,14 +625,15 @@ def _pnp_blend(layout, d, x, x2, masks, need, ndst, src_map, nvar, active, place
         return call(nsrc, chunks, int(nvar))
     if suffix == "_variants_sel":
         return call(nsrc, chunks, int(nvar), active)
-    # a table: the _placed / _resampled entries take the bitmask in every case (all bits: every variant injects)
-    name, table = ("place", place) if place is not None else ("resample", resample)
+    # a table: the _placed / _resampled / _warped entries take the bitmask in every case (all bits: every variant injects)
+    name, table = ("warp", warp) if warp is not None else ("place", place) if place is not None else ("resample", resample)
     _check_table(what, name, table, masks, nvar, d)
     return call(nsrc, chunks, int(nvar), _all_or(active, nvar), table.data_ptr())
 
 
 def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride, f_stride, p_stride, x2=None,
-                     base_chunk0=False, ndst=2, src_map=None, nvar=1, active=None, place=None, no_background=False, resample=None):
+                     base_chunk0=False, ndst=2, src_map=None, nvar=1, active=None, place=None, no_background=False, resample=None,
+                     warp=None):
     """In-place masked blend + scatter on channel-contiguous data (see include/mvoc_hip.h).  ``ndst``: trailing
     destination chunks (2 = [uncond, cond], 1 = [cond] with CFG off).  ``src_map`` = (nsrc, obj_chunks): the batch holds
     nsrc de-duplicated source chunks, object j reads chunk obj_chunks[j] (None: [bg, obj_1..obj_n], the unmapped entry).
@@ -630,12 +648,18 @@ def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride,
     per-axis maps name (scale, mirror and translation, nearest), ``masks`` are in destination coordinates -- the ``_resampled``
     entry, whatever ``nvar`` / ``src_map`` / ``active`` are.  Not with ``place``, not with a per-variant mask stack.
     A 4-D ``resample`` (``resample_table_variants``) with a [K, nobj, F, mh, mw] mask stack: a transform and masks
-    per variant -- the ``_resampled_variants`` entry."""
+    per variant -- the ``_resampled_variants`` entry.
+    ``warp``: the table of ``warp_table`` for this height x width: every object is read at the pixel its 2-D map
+    names (rotation with scale, mirror and translation, nearest), ``masks`` are in destination coordinates -- the ``_warped``
+    entry, whatever ``nvar`` / ``src_map`` / ``active`` are.  Not with ``place`` / ``resample``, a per-variant mask stack or
+    ``no_background``."""
     d = _pnp_desc(x, x2, masks, chunk_stride, f_stride, p_stride, frames, height, width, channels, base_chunk0, ndst)
     active = _active_mask(active, nvar, "pnp_blend_tokens")
     if no_background:
         if base_chunk0:
             raise RuntimeError("pnp_blend_tokens: no_background with base_chunk0: the base would be the chunk the batch does not hold")
+        if warp is not None:
+            raise RuntimeError("pnp_blend_tokens: warp= with no_background: pass src_map=(nobj, range(nobj)) instead")
         if src_map is not None or nvar != 1 or place is not None or active is not None:
             raise RuntimeError("pnp_blend_tokens: no_background is the positional entry's flag; with a source map, variants or a "
                                "placement pass src_map=(nobj, range(nobj)) instead")
@@ -644,20 +668,22 @@ def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride,
         d.base_chunk0 = -1  # (include/mvoc_hip.h: no background chunk, the base is the last chunk)
     reach = (frames - 1) * f_stride + (height * width - 1) * p_stride + channels  # of the last chunk's last element
     _pnp_blend("tokens", d, x, x2, masks, lambda nchunk: (nchunk - 1) * chunk_stride + reach, ndst, src_map, nvar, active, place,
-               resample, no_background)
+               resample, no_background, warp)
     return x
 
 
 def pnp_blend_nchw(x, masks, *, frames, x2=None, base_chunk0=True, ndst=2, src_map=None, nvar=1, active=None, place=None,
-                   resample=None):
+                   resample=None, warp=None):
     """In-place on x [(nobj+1+ndst)*F, C, H, W] (reference feature-map layout); with ``src_map`` = (nsrc, obj_chunks)
     x is [(nsrc+ndst)*F, C, H, W], with ``nvar`` = K > 1 [(nsrc+ndst*K)*F, C, H, W]; ``active`` picks the variants that are
-    written, ``place`` moves the objects, ``resample`` scales / mirrors / moves them (see ``pnp_blend_tokens``)."""
+    written, ``place`` moves the objects, ``resample`` scales / mirrors / moves them, ``warp`` also turns them (see
+    ``pnp_blend_tokens``)."""
     if x.dim() != 4 or not x.is_contiguous():
         raise RuntimeError("pnp_blend_nchw: x must be contiguous [N, C, H, W]")
     d = _pnp_desc(x, x2, masks, 0, 0, 0, frames, x.shape[2], x.shape[3], x.shape[1], base_chunk0, ndst)
     active = _active_mask(active, nvar, "pnp_blend_nchw")
-    _pnp_blend("nchw", d, x, x2, masks, lambda nchunk: nchunk * frames * x[0].numel(), ndst, src_map, nvar, active, place, resample)
+    _pnp_blend("nchw", d, x, x2, masks, lambda nchunk: nchunk * frames * x[0].numel(), ndst, src_map, nvar, active, place, resample,
+               warp=warp)
     return x
 
 
@@ -806,6 +832,114 @@ def gather_planes(src, maps, out=None):
         raise RuntimeError("gather_planes: out must be contiguous and of src's shape")
     check(lib.mvoc_gather_planes_f16(src.data_ptr(), out.data_ptr(), src.numel() // (frames * h * w), frames, h, w, maps.data_ptr(),
                                      _stream()), "gather_planes")
+    return out
+
+
+# ---- rotation: nearest resampling through ONE 2-D index map --------------------------------------------------
+def _warp_args(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw):
+    myy, myx, mxy, mxx = (int(v) for v in m)
+    dy, dx, den, ay2, ax2, H, W, Lh, Lw = (int(v) for v in (dy, dx, den, ay2, ax2, H, W, Lh, Lw))
+    if den < 1 or H < 1 or W < 1 or Lh < 1 or Lw < 1:
+        raise RuntimeError(f"level_warp_map: the denominator {den} and the sizes {H} x {W}, {Lh} x {Lw} must be positive")
+    return dy, dx, myy, myx, mxy, mxx, den, ay2, ax2, H, W, Lh, Lw
+
+
+def warp_numerator_bound(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw):
+    """an upper bound, from the arguments alone, on the magnitude of every numerator, denominator and intermediate product
+    ``level_warp_map`` forms: the vectorised int64 form is exact while it stays below 2^62"""
+    dy, dx, myy, myx, mxy, mxx, den, ay2, ax2, H, W, Lh, Lw = _warp_args(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw)
+    nyb = (2 * (H + abs(level_offset(dy, H, Lh))) + 1) * Lh + abs(ay2) * H
+    nxb = (2 * (W + abs(level_offset(dx, W, Lw))) + 1) * Lw + abs(ax2) * W
+    numy = abs(ay2) * den * H * W + abs(myy) * nyb * W + abs(myx) * nxb * H
+    numx = abs(ax2) * den * H * W + abs(mxy) * nyb * W + abs(mxx) * nxb * H
+    return max(numy, numx, 2 * den * W * Lh, 2 * den * H * Lw, H * W)
+
+
+def _level_warp_map_py(dy, dx, myy, myx, mxy, mxx, den, ay2, ax2, H, W, Lh, Lw):
+    dfy, dfx = level_offset(dy, H, Lh), level_offset(dx, W, Lw)
+    cy, cx, qy, qx = ay2 * den * H * W, ax2 * den * H * W, 2 * den * W * Lh, 2 * den * H * Lw
+    out = []
+    for iy in range(H):
+        ny = (2 * (iy - dfy) + 1) * Lh - ay2 * H
+        for ix in range(W):
+            nx = (2 * (ix - dfx) + 1) * Lw - ax2 * W
+            sy = (cy + myy * ny * W + myx * nx * H) // qy
+            sx = (cx + mxy * ny * W + mxx * nx * H) // qx
+            out.append(sy * W + sx if 0 <= sy < H and 0 <= sx < W else -1)
+    return out
+
+
+def _level_warp_map_i64(dy, dx, myy, myx, mxy, mxx, den, ay2, ax2, H, W, Lh, Lw):
+    """``_level_warp_map_py`` on int64 tensors (floor division of integers: exact) -- only below ``warp_numerator_bound`` 2^62"""
+    dfy, dfx = level_offset(dy, H, Lh), level_offset(dx, W, Lw)
+    ny = ((2 * (torch.arange(H, dtype=torch.int64) - dfy) + 1) * Lh - ay2 * H)[:, None]
+    nx = ((2 * (torch.arange(W, dtype=torch.int64) - dfx) + 1) * Lw - ax2 * W)[None, :]
+    sy = torch.div(ay2 * den * H * W + myy * W * ny + myx * H * nx, 2 * den * W * Lh, rounding_mode="floor")
+    sx = torch.div(ax2 * den * H * W + mxy * W * ny + mxx * H * nx, 2 * den * H * Lw, rounding_mode="floor")
+    inside = (sy >= 0) & (sy < H) & (sx >= 0) & (sx < W)
+    return torch.where(inside, sy * W + sx, torch.full_like(sy, -1)).reshape(-1).tolist()
+
+
+def level_warp_map(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw, form=None):
+    """the linear source pixel sy * W + sx of every destination pixel of an H x W feature grid under an Lh x Lw latent (mask)
+    grid -> a list of H * W ints, -1 where the object is absent.  ``m`` = (myy, myx, mxy, mxx) over the positive denominator
+    ``den`` is the INVERSE matrix (rows y then x): the destination pixel centre, in latent units relative to the anchor
+    (``ay2`` / 2, ``ax2`` / 2) and moved back by (``dy``, ``dx``) latent pixels (``level_offset`` carries them to this level), is
+    multiplied by it, carried back to this level and floored.  Python ints define the rule; the vectorised int64 form is taken
+    only while ``warp_numerator_bound`` stays below 2^62 (``form`` = "py" / "i64" forces one: tests).  A diagonal matrix is the
+    outer combination of ``level_axis_map`` of the two axes."""
+    args = _warp_args(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw)
+    fits = warp_numerator_bound(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw) < 2 ** 62
+    if form == "i64" and not fits:
+        raise RuntimeError("level_warp_map: the int64 form is not exact for these arguments (a numerator may reach 2^62)")
+    if form not in (None, "py", "i64"):
+        raise RuntimeError(f"level_warp_map: form {form!r} is not one of None, 'py', 'i64'")
+    return _level_warp_map_i64(*args) if fits and form != "py" else _level_warp_map_py(*args)
+
+
+def warp_maps(warp, height, width, mask_h, mask_w):
+    """``warp`` = per object (ay2, ax2, ((myy, myx, mxy, mxx, den, dy, dx) per frame)) -> nested lists [nobj][F][height * width]:
+    per frame ``level_warp_map``, computed once per distinct frame value of an object"""
+    if not warp or len({len(w[2]) for w in warp}) != 1 or not warp[0][2]:
+        raise RuntimeError("warp_maps: every object needs the same number (>= 1) of per-frame matrices")
+    rows = []
+    for ay2, ax2, frames in warp:
+        cache = {}
+        obj = []
+        for fr in frames:
+            fr = tuple(fr)
+            if fr not in cache:
+                myy, myx, mxy, mxx, den, dy, dx = fr
+                cache[fr] = level_warp_map(dy, dx, (myy, myx, mxy, mxx), den, ay2, ax2, height, width, mask_h, mask_w)
+            obj.append(cache[fr])
+        rows.append(obj)
+    return rows
+
+
+def warp_table(warp, height, width, mask_h, mask_w, device):
+    """the device table the ``_warped`` blend entries read: int32 [nobj, F, height * width] (``warp_maps``).  Every entry is in
+    [-1, height * width) by construction; the kernels treat any other value as absent as well"""
+    if height * width >= 2 ** 31:
+        raise RuntimeError(f"warp_table: {height} x {width} pixels do not fit the int32 entries")
+    return torch.tensor(warp_maps(warp, height, width, mask_h, mask_w), dtype=torch.int32).to(device).contiguous()
+
+
+def warp_planes(src, map, out=None):
+    """zero-filled per-frame gather of contiguous fp16 planes [..., F, h, w] (leading dims = planes of ONE object) through a 2-D
+    map: out[.., f, pix] = src[.., f, map_f[pix]] or 0 where the entry is outside.  ``map``: device int32 [F, h * w]."""
+    _chk(src, "src"), _chk(map, "map", torch.int32)
+    if src.dim() < 3 or not src.is_contiguous():
+        raise RuntimeError(f"warp_planes: src must be contiguous [..., F, h, w], got {tuple(src.shape)}")
+    frames, h, w = src.shape[-3:]
+    if tuple(map.shape) != (frames, h * w) or not map.is_contiguous():
+        raise RuntimeError(f"warp_planes: map must be a contiguous int32 [F = {frames}, h * w = {h * w}] table, got {tuple(map.shape)}")
+    if out is None:
+        out = torch.empty_like(src)
+    _chk(out, "out")
+    if out.shape != src.shape or not out.is_contiguous():
+        raise RuntimeError("warp_planes: out must be contiguous and of src's shape")
+    check(lib.mvoc_gather_planes_warped_f16(src.data_ptr(), out.data_ptr(), src.numel() // (frames * h * w), frames, h, w,
+                                            map.data_ptr(), _stream()), "gather_planes_warped")
     return out
 
 

@@ -15,6 +15,7 @@ iteration is one captured hipGraph replay (~2000 kernel launches otherwise).
 """
 import hashlib
 import logging
+import math
 import os
 import weakref
 from copy import deepcopy
@@ -298,9 +299,10 @@ def _downgrade_obj_transforms(out, num_frames):
     return None, tuple(out)
 
 
-def _full_obj_transforms(obj_transforms, n_obj, num_frames, lat_h, lat_w, factor=8):
+def _full_obj_transforms(obj_transforms, n_obj, num_frames, lat_h, lat_w, factor=8, rotations=None):
     """the items of ``obj_transforms`` checked and normalised -> per object the full tuple (py, qy, px, qx, flip_y, flip_x, ay2,
-    ax2, ((dy, dx) per frame)), identity and translation-only objects included"""
+    ax2, ((dy, dx) per frame)), identity and translation-only objects included.  ``rotations``: a list -- the key ``rotate`` is
+    taken as well (``resolve_obj_transforms``) and per object its per-frame (C, S) of ``_rotation`` is appended to the list"""
     if not isinstance(obj_transforms, (list, tuple)):
         raise ValueError(f"obj_transforms: needs a list of {n_obj} dicts (one per object), got {obj_transforms!r}")
     items = list(obj_transforms)
@@ -314,7 +316,7 @@ def _full_obj_transforms(obj_transforms, n_obj, num_frames, lat_h, lat_w, factor
         if not hasattr(item, "keys"):
             raise ValueError(f"{what} needs a dict with any of offset, scale, flip, anchor, got {item!r}")
         item = {k: item[k] for k in item.keys()}
-        unknown = sorted(set(item) - {"offset", "scale", "flip", "anchor"})
+        unknown = sorted(set(item) - {"offset", "scale", "flip", "anchor"} - ({"rotate"} if rotations is not None else set()))
         if unknown:
             raise ValueError(f"{what} has the unknown key(s) {', '.join(map(repr, unknown))}; the keys are offset, scale, flip, anchor")
         offs = zero
@@ -349,7 +351,77 @@ def _full_obj_transforms(obj_transforms, n_obj, num_frames, lat_h, lat_w, factor
                                  "(anchors sit on half latent pixels)")
             ax2, ay2 = 2 * anchor[0] // factor, 2 * anchor[1] // factor
         out.append((py, qy, px, qx, flip_y, flip_x, ay2, ax2, tuple(offs)))
+        if rotations is not None:
+            rot = item.get("rotate")
+            rot = 0 if rot is None else rot
+            if isinstance(rot, (list, tuple)):
+                if len(rot) != num_frames:
+                    raise ValueError(f"{what}: rotate has {len(rot)} per-frame angles, the clip {num_frames} frames")
+                rotations.append(tuple(_rotation(v, what) for v in rot))
+            else:
+                rotations.append((_rotation(rot, what),) * num_frames)
     return tuple(out)
+
+
+WARP_DEN = 65536  # D: cos and sin of ``rotate`` are rounded to multiples of 1 / D
+
+
+def _rotation(v, what):
+    """one angle of ``rotate`` (degrees: an int, a float read by its shortest decimal form or a "p/q" string; positive = counter-
+    clockwise on screen) -> (C, S) = (round(cos * D), round(sin * D)), D = ``WARP_DEN``.  Multiples of 90 degrees, taken after
+    the angle mod 360, give the exact (+-D, 0) / (0, +-D)"""
+    try:
+        if isinstance(v, bool):
+            raise ValueError
+        if isinstance(v, int):
+            fr = Fraction(v)
+        elif isinstance(v, str):
+            num, _, den = v.partition("/")
+            fr = Fraction(int(num.strip()), int(den.strip()) if den else 1)
+        elif isinstance(v, float):
+            fr = Fraction(str(v))
+        else:
+            raise ValueError
+    except (ValueError, ZeroDivisionError):
+        raise ValueError(f"{what}: rotate {v!r} is not an int, a float or a 'p/q' string of degrees") from None
+    fr = fr % 360
+    if fr % 90 == 0:
+        return ((WARP_DEN, 0), (0, WARP_DEN), (-WARP_DEN, 0), (0, -WARP_DEN))[int(fr // 90)]
+    rad = math.radians(float(fr))
+    return round(math.cos(rad) * WARP_DEN), round(math.sin(rad) * WARP_DEN)
+
+
+def _warp_of(full, rotation):
+    """one object's full transform tuple and per-frame (C, S) -> its entry of the engine's ``warp``: (ay2, ax2, ((myy, myx, mxy,
+    mxx, den, dy, dx) per frame)).  The object is scaled and mirrored about its anchor, then rotated about it, then moved, so the
+    INVERSE matrix is diag(sy * qy / py, sx * qx / px) . [[C, S], [-S, C]] / D in (y, x) order, over the common denominator
+    py * px * D and reduced by the gcd"""
+    py, qy, px, qx, flip_y, flip_x, ay2, ax2, offs = full
+    gy, gx = (-1 if flip_y else 1) * qy * px, (-1 if flip_x else 1) * qx * py
+    frames = []
+    for (c, s), (dy, dx) in zip(rotation, offs):
+        m = (gy * c, gy * s, -gx * s, gx * c, py * px * WARP_DEN)
+        g = math.gcd(*m)
+        frames.append(tuple(v // g for v in m) + (dy, dx))
+    return ay2, ax2, tuple(frames)
+
+
+def resolve_obj_transforms(obj_transforms, n_obj, num_frames, lat_h, lat_w, factor=8):
+    """``obj_transforms`` of the sampling call with the key ``rotate``: degrees, or ``num_frames`` of them (an
+    object may turn along its path) -> (placement, transform, warp), at most one of them not None:
+      every frame's matrix diagonal   what ``normalize_obj_transforms`` returns for the call without ``rotate``, exactly -- 0 and
+                                      360 degrees drop out, 180 degrees toggles both flips (the ``flip: "hv"`` call)
+      else                            warp: per object (ay2, ax2, ((myy, myx, mxy, mxx, den, dy, dx) per frame)), hashable; an
+                                      object that does not turn carries its diagonal matrix
+    Anything else is a ValueError that names the object."""
+    if obj_transforms is None:
+        return None, None, None
+    rotations = []
+    fulls = _full_obj_transforms(obj_transforms, n_obj, num_frames, lat_h, lat_w, factor, rotations)
+    if all(s == 0 and c == rot[0][0] for rot in rotations for c, s in rot):
+        folded = tuple(t if rot[0][0] > 0 else t[:4] + (not t[4], not t[5]) + t[6:] for t, rot in zip(fulls, rotations))
+        return _downgrade_obj_transforms(folded, num_frames) + (None,)
+    return None, None, tuple(_warp_of(t, rot) for t, rot in zip(fulls, rotations))
 
 
 def resolve_variant_obj_transforms(variant_obj_transforms, nvar, n_obj, num_frames, lat_h, lat_w, factor=8):
@@ -371,6 +443,10 @@ def resolve_variant_obj_transforms(variant_obj_transforms, nvar, n_obj, num_fram
         raise ValueError(f"variant_obj_transforms: {len(items)} entries for {nvar} variants (one per variant)")
     fulls = []
     for k, item in enumerate(items):
+        for j, obj in enumerate(item if isinstance(item, (list, tuple)) else ()):
+            if hasattr(obj, "keys") and "rotate" in obj.keys():
+                raise ValueError(f"variant_obj_transforms: variant {k}: object {j}: rotate: per-variant rotation is not built -- one "
+                                 "warp serves all variants of a call (obj_transforms takes rotate)")
         try:
             fulls.append(_full_obj_transforms([None] * n_obj if item is None else item, n_obj, num_frames, lat_h, lat_w, factor))
         except ValueError as e:
@@ -415,7 +491,7 @@ class CompositionState(dict):
 
 def _state_mode(st):
     """the entry of ``PLACEMENT_MODES`` a composition state was made with (``make_composition_state`` sets at most one of the
-    four values), None for a state that places nothing"""
+    five values), None for a state that places nothing"""
     return next((m for m in PLACEMENT_MODES if st.get(m.attr) is not None), None)
 
 
@@ -782,7 +858,7 @@ class I2VGenXLPipeline:
 
     # ---- composition --------------------------------------------------------------------------------------
     def _move_masks(self, masks, table, mover):
-        """per object the soft and the hard mask moved by ``mover`` (``ops.shift_planes`` / ``ops.gather_planes``, zero fill) with
+        """per object the soft and the hard mask moved by ``mover`` (``ops.shift_planes`` / ``gather_planes`` / ``warp_planes``, zero fill) with
         row j of the latent-grid ``table`` -> (masks in the form they came in, the table)"""
         dev = self.device
         moved = []
@@ -815,6 +891,18 @@ class I2VGenXLPipeline:
             raise ValueError(f"transform: every object needs {frames} per-frame offsets")
         return self._move_masks(masks, ops.resample_table(transform, h, w, h, w, self.device), ops.gather_planes)
 
+    def warp_masks(self, masks, warp):
+        """the call's masks moved to destination coordinates under a warp: per object the soft and the hard mask
+        gathered through the object's per-frame 2-D index maps of the latent grid itself (``ops.level_warp_map`` with size == mask
+        size), zero where the object is absent (``ops.warp_planes``) -> (masks in the form they came in, the device table int32
+        [nobj, F, h * w] of those maps)"""
+        if len(warp) != len(masks):
+            raise ValueError(f"warp: {len(warp)} objects, {len(masks)} masks")
+        frames, h, w = masks[0][0].shape[-3:]
+        if any(len(o[2]) != frames for o in warp):
+            raise ValueError(f"warp: every object needs {frames} per-frame matrices")
+        return self._move_masks(masks, ops.warp_table(warp, h, w, h, w, self.device), ops.warp_planes)
+
     def _move_variant_masks(self, masks, values, move, tables_key):
         """the call's masks moved once per variant by ``move`` (``place_masks`` / ``transform_masks``) with each of ``values`` ->
         dict(``tables_key`` = per variant the device table of its move on the latent grid,
@@ -835,7 +923,7 @@ class I2VGenXLPipeline:
         return self._move_variant_masks(masks, variant_transforms, self.transform_masks, "resample_dev")
 
     def make_composition_state(self, latents, cond, masks, guidance_scale, dedup_sources=None, variants=1, placement=None,
-                               variant_placements=None, transform=None, variant_transforms=None):
+                               variant_placements=None, transform=None, variant_transforms=None, warp=None):
         """static buffers + the captured iteration variants of the composition loop.
         cond: dict(encoder_hidden_states [n,77,D], image_embeddings [n,F,D], image_latents_first, image_latents, fps).
         The state keeps its OWN copy of ``cond``: the hoisted conditioning (``prepare_conditioning``) and the shared-CFG-prefix
@@ -855,14 +943,17 @@ class I2VGenXLPipeline:
         here, to destination coordinates (``transform_masks``); the fusion steps gather the objects' latents the same way.
         ``variant_transforms`` (``resolve_variant_obj_transforms``; not with any of the three above): K transforms,
         one per variant.  Each variant's masks are gathered once, here; the engine takes them as (soft, hard) [K, nobj, F, h, w]
-        stacks, the fusion steps each variant's own.  The hooks keep ``masks`` as they came (shape checks and the mask key)."""
+        stacks, the fusion steps each variant's own.  The hooks keep ``masks`` as they came (shape checks and the mask key).
+        ``warp`` (``resolve_obj_transforms``; not with any of the four above): rotation with scale, mirror and
+        translation per object and frame, one warp for all variants.  ``masks`` come in source coordinates and are gathered ONCE,
+        here, through the 2-D maps of the latent grid (``warp_masks``); the fusion steps gather the objects' latents the same way."""
         cond = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in cond.items()}
         given = {"placement": placement, "variant_placements": variant_placements, "transform": transform,
-                 "variant_transforms": variant_transforms}
-        # the state's keys of the four modes: each mode's value, the shared modes' latent-grid table (place_dev / resample_dev)
+                 "variant_transforms": variant_transforms, "warp": warp}
+        # the state's keys of the five modes: each mode's value, the shared modes' latent-grid table (place_dev / resample_dev)
         # and the per-variant modes' ``_move_variant_masks`` dict (vplace / vresample); all None but the active mode's
         placed = dict.fromkeys(("placement", "place_dev", "variant_placements", "vplace", "transform", "resample_dev",
-                                "variant_transforms", "vresample"))
+                                "variant_transforms", "vresample", "warp", "warp_dev"))
         on = [m for m in PLACEMENT_MODES if given[m.attr] is not None]
         if on:
             m = on[0]
@@ -873,7 +964,7 @@ class I2VGenXLPipeline:
                 raise RuntimeError(frame_shard_refusal(m.subject, m.mover))
             if m.per_variant and len(value) != int(variants):
                 raise ValueError(f"{m.attr}: {len(value)} {m.items} for {int(variants)} variants")
-            move = self.transform_masks if m.kw == "resample" else self.place_masks
+            move = {"resample": self.transform_masks, "place": self.place_masks, "warp": self.warp_masks}[m.kw]
             if m.per_variant:
                 value = tuple(tuple(v) for v in value)
                 placed["v" + m.kw] = self._move_variant_masks(masks, value, move, m.kw + "_dev")
@@ -952,7 +1043,7 @@ class I2VGenXLPipeline:
                           prune_background=bool(self.prune_background),  # ... and never the background's output
                           shared_prefix_chunks=2 if st["share_cfg_prefix"] else 0, source_chunks=smap, variants=nvar,
                           placement=st["placement"], variant_placements=st["variant_placements"], transform=st["transform"],
-                          variant_transforms=st["variant_transforms"], variant_masks=None if vstate is None else vstate["masks"]):
+                          variant_transforms=st["variant_transforms"], warp=st["warp"], variant_masks=None if vstate is None else vstate["masks"]):
                 noise = u.forward_ext(inp, st["t"], mcond["fps"], mcond["image_latents_first"], mcond["image_latents"],
                                       mcond["image_embeddings"], mcond["encoder_hidden_states"], multi_frame_guidance=False,
                                       conditioning=prepared)[0]
@@ -1063,7 +1154,10 @@ class I2VGenXLPipeline:
         the optional keys ``offset`` (an ``obj_offsets`` item), ``scale`` (s or [sx, sy]: int, "p/q" or float; p, q <= 64),
         ``flip`` (None, "h", "v", "hv") and ``anchor`` ([ax, ay], image pixels in multiples of 4; default the frame centre) --
         the object is scaled and mirrored about the anchor (nearest neighbour, exact) and then moved, without re-inverting
-        anything (``normalize_obj_transforms``; shared by the variants, not with a frame shard).  Every object at identity:
+        anything (``normalize_obj_transforms``; shared by the variants, not with a frame shard).  ``rotate``: degrees
+        counter-clockwise on screen (int, float or "p/q"), or ``num_frames`` of them -- the object is scaled and mirrored about
+        its anchor, then turned about it, then moved (nearest, ``resolve_obj_transforms``); 0 / 360 are the call without the key,
+        180 the ``flip: "hv"`` call.  Not inside ``variant_obj_transforms``.  Every object at identity:
         exactly a call without it; translation only: exactly the ``obj_offsets`` call.  ``obj_width_height`` stays ignored.
 
         ``variant_obj_transforms`` (not together with any of the three above): a list of K items, one per variant,
@@ -1126,17 +1220,17 @@ class I2VGenXLPipeline:
         if variant_obj_offsets is not None:
             placement, variant_placements = resolve_variant_obj_offsets(variant_obj_offsets, nvar, n_obj, num_frames,
                                                                         self.vae_scale_factor)
-        transform = None
+        transform = warp = None
         if obj_transforms is not None:
-            placement, transform = normalize_obj_transforms(obj_transforms, n_obj, num_frames, height // self.vae_scale_factor,
-                                                            width // self.vae_scale_factor, self.vae_scale_factor)
+            placement, transform, warp = resolve_obj_transforms(obj_transforms, n_obj, num_frames, height // self.vae_scale_factor,
+                                                                width // self.vae_scale_factor, self.vae_scale_factor)
         variant_transforms = None
         if variant_obj_transforms is not None:
             placement, variant_placements, transform, variant_transforms = resolve_variant_obj_transforms(
                 variant_obj_transforms, nvar, n_obj, num_frames, height // self.vae_scale_factor, width // self.vae_scale_factor,
                 self.vae_scale_factor)
         placed = {"placement": placement, "variant_placements": variant_placements, "transform": transform,
-                  "variant_transforms": variant_transforms}  # (at most one is not None: each resolver returns one)
+                  "variant_transforms": variant_transforms, "warp": warp}  # (at most one is not None: each resolver returns one)
         for m in PLACEMENT_MODES:
             if placed[m.attr] is not None and self.unet.shard is not None:
                 raise RuntimeError(frame_shard_refusal(m.arg + " do", m.mover))

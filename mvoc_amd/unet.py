@@ -617,7 +617,7 @@ class Conditioning:
         return self
 
 
-# The four ways to place objects at composition time (how they are resolved: 6p), highest precedence first:
+# The five ways to place objects at composition time (how they are resolved: 6p), highest precedence first:
 # when several are set the first one's ``mix`` sentence is raised.  Per mode: the engine attribute (also the argument and key of the
 # pipeline's composition state), whether it holds one value per variant, the blend keyword its table goes to, the ``ops`` builder
 # of that table, how it moves a plane (``ops.<mover>_planes``), and the words of its messages -- the subject of the frame-shard
@@ -625,6 +625,9 @@ class Conditioning:
 # ("set" on the engine, "given" in the pipeline).
 _Mode = namedtuple("_Mode", "attr per_variant kw builder mover subject arg items holds mix")
 PLACEMENT_MODES = (
+    _Mode("warp", False, "warp", "warp_table", "warp", "a warp does", "obj_transforms", None, "",
+          "warp is {set} together with placement / variant_placements / transform / variant_transforms: the warp's matrix carries "
+          "scale, mirror and translation, and one warp serves all variants"),
     _Mode("variant_transforms", True, "resample", "resample_table_variants", "gather", "variant_transforms do",
           "variant_obj_transforms", "transforms", "",
           "variant_transforms is {set} together with placement / variant_placements / transform: every variant's transform "
@@ -709,9 +712,9 @@ class I2VGenXLUNet:
         # paired attention serves the K pairs in one launch.  1 = today's batch, kernels and launches.  Set and restored around
         # its forward by the composition loop, like source_chunks.  Not with a frame shard, not with shared_prefix_chunks.
         self.variants = 1
-        # Object placement at composition time: four mutually exclusive modes (PLACEMENT_MODES), each None = today's calls.  All four
+        # Object placement at composition time: five mutually exclusive modes (PLACEMENT_MODES), each None = today's calls.  All five
         # are set and restored around its forward by the composition loop, like source_chunks, and none combines with a frame
-        # shard or with another of the four: ``_placement_mode`` resolves which is on, and refuses, when a site asks.  The hook
+        # shard or with another of the five: ``_placement_mode`` resolves which is on, and refuses, when a site asks.  The hook
         # mask lists carry ONE mask set in every mode (shape checks and the mask key).
         # Placement (pipeline.py obj_offsets): a hashable tuple -- per object, per frame (dy, dx) on the latent grid
         # (the masks' h x w).  Every injection site then reads object j of frame f at its shifted pixel through the _placed blend
@@ -735,6 +738,12 @@ class I2VGenXLUNet:
         # anchor at the frame centre, zero offsets).  Every injection site then passes ``variant_masks`` -- variant k's masks
         # gathered with ITS maps -- and the per-level [K, nobj, F, H + W] table to the _resampled_variants blend entries.
         self.variant_transforms = None
+        # Rotation (pipeline.py obj_transforms with ``rotate``): a hashable tuple -- per object (ay2, ax2, ((myy, myx,
+        # mxy, mxx, den, dy, dx) per frame)): twice the anchor, and per frame the INVERSE matrix as four ints over one positive
+        # denominator (rows y then x) with the translation, all on the latent grid.  Every injection site then reads object j of
+        # frame f at the pixel its 2-D map names (ops.level_warp_map for the site's H x W) through the _warped blend entries; the
+        # hook masks are in destination coordinates already (the pipeline gathers them once per call).  Shared by the variants.
+        self.warp = None
         # the modes' device tables: attribute name -> (value, {(H, W, mh, mw): table}); a mode's tables are dropped when ITS value
         # changes, so states of different modes that step alternately keep theirs
         self._level_tables = {m.attr: (None, {}) for m in PLACEMENT_MODES}
@@ -945,7 +954,7 @@ class I2VGenXLUNet:
         return nsrc, chunks
 
     def _placement_mode(self, mask_list=None):
-        """the one place that reads the four placement attributes: None when no object is placed, else the active entry of
+        """the one place that reads the five placement attributes: None when no object is placed, else the active entry of
         ``PLACEMENT_MODES``.  Refused here, in this order: two modes at once (the message of the one that comes first in
         PLACEMENT_MODES), a frame shard and -- given the hooks' ``mask_list`` -- a value that does not hold one entry per variant
         and, in each, one per object"""
@@ -969,8 +978,9 @@ class I2VGenXLUNet:
 
     def place_kw(self, mask_list, H, W):
         """keyword arguments of a site's blend call: none without a placement or transform (exactly today's call), else
-        ``place=`` -- or, under ``transform`` / ``variant_transforms``, ``resample=`` -- the level's device table: [nobj, F, 2]
-        offsets or [nobj, F, H + W] per-axis index maps, with a leading K in the per-variant modes.  Built once per (value, H, W,
+        ``place=`` -- or, under ``transform`` / ``variant_transforms``, ``resample=``, under ``warp``, ``warp=`` -- the level's
+        device table: [nobj, F, 2] offsets, [nobj, F, H + W] per-axis index maps (a leading K in the per-variant modes) or the
+        [nobj, F, H * W] 2-D index map.  Built once per (value, H, W,
         mh, mw) and dropped when the mode's value changes"""
         m = self._placement_mode(mask_list)
         if m is None:

@@ -20,7 +20,7 @@ also runs the K compositions one by one in the same process and reports the rati
 --place "dx,dy;dx,dy" (opt-in): the entry's `obj_offset` (DESIGN.md 6k) -- one pair per object, image pixels in multiples of 8;
 the composition then places the objects that far from where they sit in their clips.  Reported like --variants (K = 1 unless
 --variants is given too).
---transform "scale=3/2,flip=h,offset=64,0;scale=1/2" (opt-in): the entry's `obj_transform` -- one item per object:
+--transform "scale=3/2,flip=h,offset=64,0;scale=1/2" (opt-in): the entry's `obj_transform` (`rotate=30` turns an object, 6q) -- one item per object:
 scale (s or sx,sy; ints or p/q), flip (h, v, hv), offset (dx,dy) and anchor (ax,ay); nearest-neighbour scale and mirror about the
 anchor, then the offset.  Reported like --place.
 --variant-place "dx,dy;dx,dy|dx,dy;dx,dy|.." (opt-in, needs --variants K): K placements separated by `|`, each in the format of
@@ -378,7 +378,8 @@ def parse_place(text):
 
 def parse_transform(text):
     """"scale=3/2,flip=h,offset=64,0;scale=1/2" -> one dict per object (`;` separates the objects): the entry's `obj_transform`.
-    scale = s or sx,sy (ints or p/q); flip = h, v or hv; offset = dx,dy; anchor = ax,ay; an empty item is the identity"""
+    scale = s or sx,sy (ints or p/q); flip = h, v or hv; offset = dx,dy; anchor = ax,ay; rotate = degrees (an int, a decimal or
+    p/q; counter-clockwise) or one angle per frame; an empty item is the identity"""
     out = []
     for j, item in enumerate(text.split(";")):
         fields = []
@@ -389,7 +390,7 @@ def parse_transform(text):
             elif fields:
                 fields[-1][1].append(tok)
             else:
-                raise SystemExit(f"--transform, object {j}: {tok!r} has no key (scale=, flip=, offset=, anchor=)")
+                raise SystemExit(f"--transform, object {j}: {tok!r} has no key (scale=, flip=, offset=, anchor=, rotate=)")
         d = {}
         for k, vals in fields:
             try:
@@ -400,6 +401,9 @@ def parse_transform(text):
                     d[k] = vals[0]
                 elif k in ("offset", "anchor") and len(vals) == 2:
                     d[k] = [int(v) for v in vals]
+                elif k == "rotate" and vals:
+                    deg = [int(v) if v.lstrip("+-").isdigit() else v if "/" in v else float(v) for v in vals]
+                    d[k] = deg[0] if len(deg) == 1 else deg
                 else:
                     raise ValueError
             except ValueError:
@@ -567,8 +571,8 @@ if __name__ == "__main__":
                     help="place the objects at composition time: one dx,dy per object, image pixels in multiples of 8 (`obj_offset`)")
     ap.add_argument("--variant-place", type=str, default=None, metavar="dx,dy;dx,dy|..",
                     help="with --variants K: K placements separated by |, each in the format of --place (the variants' `placement` key)")
-    ap.add_argument("--transform", type=str, default=None, metavar="scale=p/q,flip=h,offset=dx,dy;..",
-                    help="scale / mirror / place the objects at composition time: one item per object separated by ; (`obj_transform`)")
+    ap.add_argument("--transform", type=str, default=None, metavar="scale=p/q,flip=h,offset=dx,dy,rotate=deg;..",
+                    help="scale / mirror / turn / place the objects at composition time: one item per object separated by ; (`obj_transform`)")
     ap.add_argument("--variant-transform", type=str, default=None, metavar="scale=p/q,flip=h;..|..",
                     help="with --variants K: K transforms separated by |, each in the format of --transform (the variants' "
                          "`transform` key); an empty item leaves that variant untransformed")
