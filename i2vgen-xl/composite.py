@@ -160,12 +160,26 @@ def variant_placement_kwargs(config, variants):
                                     for c in variants]}
 
 
+def _filter_kwargs(config):
+    """the entry's optional ``obj_transform_filter`` ("nearest" or "bilinear"; next to ``obj_transform``) -> the
+    sampling call's keyword of that name; absent or None: no keyword (exactly today's call).  Any other value is refused here,
+    whatever else the entry sets"""
+    if "obj_transform_filter" not in config or config.obj_transform_filter is None:
+        return {}
+    value = config.obj_transform_filter
+    if value not in ("nearest", "bilinear"):
+        raise ValueError(f"obj_transform_filter {value!r} is not one of 'nearest', 'bilinear'")
+    return {"obj_transform_filter": str(value)}
+
+
 def transform_kwargs(config, variants=None):
     """the entry's optional ``obj_transform`` (one dict per object: ``offset``, ``scale``, ``flip``, ``anchor``, ``rotate``)
     with the placements of ``variant_placement_kwargs``: none of the keys -> {} (exactly today's call); ``obj_transform`` alone
     -> ``obj_transforms`` as plain dicts and lists (the call checks and normalises them; shared by the entry's variants: not one
     of ``VARIANT_KEYS``); together with ``obj_offset`` or any variant's ``placement`` it is an error -- a transform carries its
     own offset.  ``obj_width_height`` stays ignored, as in the reference.
+    ``obj_transform_filter`` ("nearest" / "bilinear") goes with ``obj_transform`` to the call as it is; "bilinear"
+    without ``obj_transform`` or next to a variant's ``transform`` is an error, and so is any other value.
     A variant's ``transform`` (the format of ``obj_transform``) transforms the objects for that variant alone:
     ``variant_obj_transforms`` = one item per variant -- the variant's ``transform``, or the entry's ``obj_transform`` (None
     without one) for a variant that does not set the key; not with the entry's ``obj_offset`` or any variant's ``placement``."""
@@ -174,7 +188,11 @@ def transform_kwargs(config, variants=None):
             return {str(k): plain(v[k]) for k in v.keys()}
         return [plain(x) for x in v] if hasattr(v, "__iter__") and not isinstance(v, (str, bytes)) else v
 
+    bilinear = _filter_kwargs(config).get("obj_transform_filter") == "bilinear"  # (a misspelt value is refused in every case)
     if variants is not None and any("transform" in c and c.transform is not None for c in variants):
+        if bilinear:
+            raise ValueError("obj_transform_filter is 'bilinear' and a variant sets 'transform': the filter samples the objects of "
+                             "obj_transform, one filter for all variants (per-variant warps are not built)")
         if "obj_offset" in config and config.obj_offset is not None:
             raise ValueError("a variant sets 'transform' and the entry sets obj_offset: put the offset into the transform ('offset')")
         if any("placement" in c and c.placement is not None for c in variants):
@@ -184,12 +202,15 @@ def transform_kwargs(config, variants=None):
         return {"variant_obj_transforms": [plain(c.transform) if "transform" in c and c.transform is not None else shared
                                            for c in variants]}
     if "obj_transform" not in config or config.obj_transform is None:
+        if bilinear:
+            raise ValueError("obj_transform_filter is 'bilinear' without obj_transform: the filter samples the entry's transformed "
+                             "objects")
         return variant_placement_kwargs(config, variants)
     if "obj_offset" in config and config.obj_offset is not None:
         raise ValueError("obj_transform and obj_offset are both set: put the offset into the transform ('offset')")
     if variants is not None and any("placement" in c and c.placement is not None for c in variants):
         raise ValueError("obj_transform is set and a variant sets 'placement': one transform serves all variants of an entry")
-    return {"obj_transforms": plain(config.obj_transform)}
+    return {"obj_transforms": plain(config.obj_transform), **_filter_kwargs(config)}
 
 
 def variant_output_dir(config, k):

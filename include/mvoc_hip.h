@@ -493,6 +493,34 @@ int mvoc_pnp_blend_scatter_nchw_warped(const mvoc_pnp_desc* d, int32_t nsrc, con
  * mvoc_shift_planes_f16).  Every int32 entry is valid (compared unsigned).  Refuses what mvoc_gather_planes_f16 refuses. */
 int mvoc_gather_planes_warped_f16(const void* src, void* dst, int32_t nplane, int32_t frames, int32_t h, int32_t w,
                                   const int32_t* map, void* stream);
+/* Bilinear sampling: the _warped entries with a TAP table in place of the 2-D map; the blend sites are those of the
+ * family (pnp_utils.py:624-672, 778-850 for tokens; :970-1004, 1059-1082, 1114-1146 for nchw).  `taps` is a DEVICE table of int32
+ * [nobj][frames][height * width][2] for THIS call's height x width; the pair of destination pixel (py, px) of object j, frame f is
+ *     word 0 = ((y0 + 1) << 16) | (x0 + 1)    the upper-left tap, y0 in [-1, height - 1], x0 in [-1, width - 1]; -1 = absent
+ *     word 1 = (qy << 16) | qx                weights in 1/256 of the LOWER row y0 + 1 and the RIGHT column x0 + 1 (9 bits are read)
+ * The value of a tap (y0, x0), (y0, x0 + 1), (y0 + 1, x0), (y0 + 1, x0 + 1) is used only if (uint32_t)row < height && (uint32_t)col <
+ * width; a tap outside loads the plane's pixel 0 instead (always in bounds) and enters as +0.0: EVERY int32 pair is safe.  Value, one correctly rounded fp16 operation per statement, with
+ * lerp(a, b, w0, w1) = r16(r16(a * w0) + r16(b * w1)) and fp16 weights wx1 = qx / 256, wx0 = (256 - qx) / 256 (same for y):
+ *     top = lerp(v00, v01, wx0, wx1);  bot = lerp(v10, v11, wx0, wx1);  v = lerp(top, bot, wy0, wy1)
+ * The object is present iff at least one tap lies inside the plane (a tap of weight 0 counts); absent: value 0 and mask 0 enter
+ * the same three fp16-rounded blend ops (nothing is skipped).  A tap inside the plane is multiplied even with weight 0 (inf in a
+ * source gives NaN), and -0.0 leaves the chain as +0.0.  Masks (DESTINATION coordinates), object order, ndst, base_chunk0, the
+ * source map, nvar and `active` are those of _warped.  The destination rows are bit-identical to the unplaced entries on object
+ * chunks interpolated beforehand by this chain, with masks zeroed where the object is absent; a table with q = 0 everywhere is
+ * the _warped entry with the map y0 * width + x0 (for sources without -0.0).  Bytes counted per launch (MvocProfScope): those of
+ * _placed (each distinct object chunk once) + 8 * nobj*frames*height*width for the table.  The table's contents are on the device
+ * and are not read by the host.  The caller owns the table and keeps it unchanged while a captured graph may replay the launch.
+ * Requires what _warped requires (-1 / -2 and an error text, nothing written) and height, width < 65535 (else -2). */
+int mvoc_pnp_blend_scatter_tokens_bilinear(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
+                                           uint32_t active, const int32_t* taps, void* stream);
+int mvoc_pnp_blend_scatter_nchw_bilinear(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
+                                         uint32_t active, const int32_t* taps, void* stream);
+/* Zero-filled per-frame bilinear gather of contiguous fp16 planes [nplane][frames][h][w] (src != dst): dst[pl][f][y][x] = the
+ * chain above on the four taps of taps_f[y * w + x] read from src[pl][f], 0 where no tap lies inside the plane.  `taps`: DEVICE
+ * int32 [frames][h * w][2], shared by the nplane planes.  Every int32 pair is valid.  Refuses what mvoc_gather_planes_warped_f16
+ * refuses, and h or w >= 65535 (-2). */
+int mvoc_gather_planes_bilinear_f16(const void* src, void* dst, int32_t nplane, int32_t frames, int32_t h, int32_t w,
+                                    const int32_t* taps, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Loop glue on [B,4,F,h,w] fp16 latents, BIT-EXACT vs the reference's eager fp16 op chain.

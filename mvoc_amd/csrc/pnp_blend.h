@@ -1,7 +1,8 @@
 // The pieces of the blend-scatter family that more than one translation unit composes its kernels
 // from: the argument block and what fills / refuses it, the fp16 blend, the two item geometries with their object loads, the
 // per-variant scatter and the host launch path.  pnp.hip holds the family's ten kernels (and the text that describes the
-// pieces); pnp_variants2.hip the per-variant MAP form; pnp_warp.hip the MAP2 form (a 2-D index map: rotation).
+// pieces); pnp_variants2.hip the per-variant MAP form; pnp_warp.hip the MAP2 form (a 2-D index map: rotation);
+// pnp_bilinear.hip the TAPS form (four taps and fixed-point weights per pixel: bilinear sampling).
 // Everything is in an anonymous namespace: each unit gets its own copy.
 #pragma once
 #include <type_traits>
@@ -106,7 +107,69 @@ __device__ __forceinline__ bool warped_src(const int* __restrict__ map, int j, i
   return s < (unsigned)(h * w);
 }
 
-enum Src { DIRECT, SHIFT, MAP, MAP2 };
+enum Src { DIRECT, SHIFT, MAP, MAP2, TAPS };
+
+// TAPS: taps = int32 [nobj][frames][height * width][2], bilinear sampling on an exact fp16 chain.  Word 0 =
+// ((y0 + 1) << 16) | (x0 + 1) names the upper-left tap (y0 in [-1, h - 1], x0 in [-1, w - 1]; -1 by convention where the object is
+// absent), word 1 = (qy << 16) | qx the weights of the LOWER row and the RIGHT column in 1/256 (9 bits each are read).  A tap's
+// VALUE is used only if (unsigned)row < h && (unsigned)col < w; a tap outside still issues a load, of the plane's pixel 0 (always in
+// bounds), and the loaded bits are ANDed to +0.0 before they enter the chain -- so every int32 pair is safe and no load is behind
+// a branch.  The object is present iff at least one tap is inside the plane.  lerp16_h is blend16_h with free weights: one correctly rounded fp16 operation per statement.
+__device__ __forceinline__ half_t lerp16_h(half_t a, half_t b, half_t w0, half_t w1) {
+  const half_t x = a * w0;
+  const half_t y = b * w1;
+  return x + y;
+}
+
+struct Taps {
+  int s[4];       // source pixels of the taps (y0, x0), (y0, x0 + 1), (y0 + 1, x0), (y0 + 1, x0 + 1); 0 where the tap is outside
+  unsigned bits;  // bit k: tap k is inside the plane; bit 4: any of them is (the object is present)
+  half_t wx0, wx1, wy0, wy1;
+};
+
+// The flags travel as ONE opaque VGPR per (object, pixel) and each becomes an all-ones / zero AND mask where it is used: as bools
+// they are wave-wide conditions in SGPR pairs that stay live across the loads, and the 8-pixel NCHW forms spill SGPRs.  A value
+// whose tap is outside is ANDed to +0.0.
+__device__ __forceinline__ unsigned short tap_mask(unsigned bits, int k) {
+  return (unsigned short)(-(int)((bits >> k) & 1u));
+}
+
+__device__ __forceinline__ half_t tap_and(half_t v, unsigned short m) {
+  unsigned short u;
+  __builtin_memcpy(&u, &v, 2);
+  u &= m;
+  __builtin_memcpy(&v, &u, 2);
+  return v;
+}
+
+__device__ __forceinline__ Taps taps_src(const int* __restrict__ taps, int j, int frames, int f, int py, int px, int h, int w) {
+  const int2 t = *reinterpret_cast<const int2*>(taps + ((((long)j * frames + f) * h + py) * w + px) * 2);
+  const unsigned r0 = ((unsigned)t.x >> 16) - 1u, c0 = ((unsigned)t.x & 0xffffu) - 1u;
+  const unsigned r1 = r0 + 1u, c1 = c0 + 1u;
+  const bool ri0 = r0 < (unsigned)h, ri1 = r1 < (unsigned)h, ci0 = c0 < (unsigned)w, ci1 = c1 < (unsigned)w;
+  Taps o;
+  o.s[0] = ri0 && ci0 ? (int)(r0 * w + c0) : 0;
+  o.s[1] = ri0 && ci1 ? (int)(r0 * w + c1) : 0;
+  o.s[2] = ri1 && ci0 ? (int)(r1 * w + c0) : 0;
+  o.s[3] = ri1 && ci1 ? (int)(r1 * w + c1) : 0;
+  o.bits = (ri0 && ci0 ? 1u : 0u) | (ri0 && ci1 ? 2u : 0u) | (ri1 && ci0 ? 4u : 0u) | (ri1 && ci1 ? 8u : 0u) |
+           ((ri0 || ri1) && (ci0 || ci1) ? 16u : 0u);
+  asm volatile("" : "+v"(o.bits));
+  const int qy = (t.y >> 16) & 0x1ff, qx = t.y & 0x1ff;
+  const half_t u = (half_t)0.00390625f;  // 1/256: the products are exact for q <= 256
+  o.wx0 = (half_t)(256 - qx) * u, o.wx1 = (half_t)qx * u;
+  o.wy0 = (half_t)(256 - qy) * u, o.wy1 = (half_t)qy * u;
+  return o;
+}
+
+// the four loaded values -> the interpolated value (0 where the object is absent)
+__device__ __forceinline__ half_t taps_value(const Taps& t, half_t v00, half_t v01, half_t v10, half_t v11) {
+  v00 = tap_and(v00, tap_mask(t.bits, 0)), v01 = tap_and(v01, tap_mask(t.bits, 1));
+  v10 = tap_and(v10, tap_mask(t.bits, 2)), v11 = tap_and(v11, tap_mask(t.bits, 3));
+  const half_t top = lerp16_h(v00, v01, t.wx0, t.wx1);
+  const half_t bot = lerp16_h(v10, v11, t.wx0, t.wx1);
+  return tap_and(lerp16_h(top, bot, t.wy0, t.wy1), tap_mask(t.bits, 4));
+}
 
 template <Src S>
 __device__ __forceinline__ bool obj_src(const int* __restrict__ tab, int j, int frames, int f, int py, int px, int h, int w,
@@ -187,6 +250,20 @@ struct Tokens {
       if constexpr (S == DIRECT) {
         o.m[j][0] = (float)masks[mask_index(p, j, f, my, mx)];
         ld_vec<8>(o.v[j], src + off);
+      } else if constexpr (S == TAPS) {
+        // the four vectors are loaded without a branch (a tap outside reads pixel 0 and is ANDed to +0.0): all four loads are in
+        // flight before the first is consumed
+        const Taps t = taps_src(tab, j, p.frames, f, py, px, p.height, p.width);
+        half_t v[4][8];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ld_vec<8>(v[k], src + foff + (long)t.s[k] * p.p_stride);
+        o.m[j][0] = tap_and(masks[mask_index(p, j, f, my, mx)], tap_mask(t.bits, 4));
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o.v[j][e] = taps_value(t, v[0][e], v[1][e], v[2][e], v[3][e]);
+        // 3 and 4 objects: an opaque use of the finished vector, so that this object's interpolation ends before the next
+        // object's loads are issued -- with all sixteen tap vectors in flight the kernel needs 74 / 108 VGPRs (6 / 4 waves), this
+        // way 57 (8 waves)
+        if constexpr (NOBJ > 2) asm volatile("" : "+v"(*reinterpret_cast<half8_t*>(o.v[j])));
       } else {
         long spix;
         const bool in = obj_src<S>(tab, j, p.frames, f, py, px, p.height, p.width, spix);
@@ -265,14 +342,24 @@ struct Nchw {
         for (int e = 0; e < VEC; ++e) {
           const int pix = pv * VEC + e;
           const int py = pix / p.width, px = pix - py * p.width;
-          long spix;
-          const bool in = obj_src<S>(tab, j, p.frames, f, py, px, p.height, p.width, spix);
-          o.m[j][e] = (half_t)0.0f;
-          o.v[j][e] = (half_t)0.0f;
-          if (in) {
+          if constexpr (S == TAPS) {
+            const Taps t = taps_src(tab, j, p.frames, f, py, px, p.height, p.width);
+            half_t v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = src[t.s[k]];
             const int my = nearest_src(py, p.sy, p.mask_h), mx = nearest_src(px, p.sx, p.mask_w);
-            o.m[j][e] = masks[(mrow + my) * p.mask_w + mx];
-            o.v[j][e] = src[spix];
+            o.m[j][e] = tap_and(masks[(mrow + my) * p.mask_w + mx], tap_mask(t.bits, 4));
+            o.v[j][e] = taps_value(t, v[0], v[1], v[2], v[3]);
+          } else {
+            long spix;
+            const bool in = obj_src<S>(tab, j, p.frames, f, py, px, p.height, p.width, spix);
+            o.m[j][e] = (half_t)0.0f;
+            o.v[j][e] = (half_t)0.0f;
+            if (in) {
+              const int my = nearest_src(py, p.sy, p.mask_h), mx = nearest_src(px, p.sx, p.mask_w);
+              o.m[j][e] = masks[(mrow + my) * p.mask_w + mx];
+              o.v[j][e] = src[spix];
+            }
           }
         }
       }

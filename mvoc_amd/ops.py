@@ -549,12 +549,22 @@ def _active_mask(active, nvar, what):
     return None if active == (1 << nvar) - 1 else active
 
 
-def _blend_entry(what, place, resample, mask_dim, no_background, src_map, nvar, active, warp=None):
+def _blend_entry(what, place, resample, mask_dim, no_background, src_map, nvar, active, warp=None, warp_taps=None):
     """the suffix of the library entry mvoc_pnp_blend_scatter_<layout><suffix> that the arguments of ``pnp_blend_<layout>``
     select, by the form of ``place`` / ``resample`` (None, a 3-D table shared by the variants, a 4-D table per variant) and of the
     masks (4-D, or a 5-D [K, nobj, F, mh, mw] stack, which goes with a 4-D table only), or by ``warp`` (a 3-D table shared by the
-    variants); every other combination is refused"""
+    variants) or ``warp_taps`` (a 4-D tap table shared by the variants); every other combination is
+    refused"""
     dim = lambda t: t.dim() if torch.is_tensor(t) else None
+    if warp_taps is not None:
+        if place is not None or resample is not None or warp is not None:
+            raise RuntimeError(f"{what}: warp_taps= is given together with place= / resample= / warp=: the tap table carries the "
+                               "whole warp")
+        if mask_dim == 5:
+            raise RuntimeError(f"{what}: warp_taps= does not take a [K, nobj, F, mh, mw] mask stack: one warp serves all variants")
+        if no_background:
+            raise RuntimeError(f"{what}: warp_taps= with no_background: pass src_map=(nobj, range(nobj)) instead")
+        return "_bilinear"
     if warp is not None:
         if place is not None or resample is not None:
             raise RuntimeError(f"{what}: warp= is given together with place= / resample=: the 2-D map carries scale, mirror and "
@@ -582,10 +592,17 @@ def _blend_entry(what, place, resample, mask_dim, no_background, src_map, nvar, 
 
 
 def _check_table(what, name, table, masks, nvar, d):
-    """the form of a ``place`` ([.., 2]), ``resample`` ([.., H + W]) or ``warp`` ([nobj, F, H * W], never per variant) table
+    """the form of a ``place`` ([.., 2]), ``resample`` ([.., H + W]), ``warp`` ([nobj, F, H * W], never per variant) or
+    ``warp_taps`` ([nobj, F, H * W, 2], never per variant) table
     against the descriptor: int32 [nobj, F, ..], or per variant [K, nobj, F, ..] next to a [K, nobj, F, mh, mw]
     mask stack"""
     _chk(table, name, torch.int32)
+    if name == "warp_taps":
+        shape = (d.nobj, d.frames, d.height * d.width, 2)
+        if tuple(table.shape) != shape or not table.is_contiguous():
+            raise RuntimeError(f"{what}: warp_taps must be a contiguous int32 [nobj = {d.nobj}, F = {d.frames}, H * W = {shape[2]}, 2] "
+                               f"table, got {tuple(table.shape)}")
+        return
     if name == "warp":
         shape = (d.nobj, d.frames, d.height * d.width)
         if tuple(table.shape) != shape or not table.is_contiguous():
@@ -604,12 +621,13 @@ def _check_table(what, name, table, masks, nvar, d):
                            f"contiguous [{dims}, mh, mw] stack, got {tuple(masks.shape)}")
 
 
-def _pnp_blend(layout, d, x, x2, masks, need, ndst, src_map, nvar, active, place, resample, no_background=False, warp=None):
+def _pnp_blend(layout, d, x, x2, masks, need, ndst, src_map, nvar, active, place, resample, no_background=False, warp=None,
+               warp_taps=None):
     """call the library entry mvoc_pnp_blend_scatter_<layout><suffix> that the arguments of ``pnp_blend_<layout>`` select
     (``_blend_entry``) on the descriptor ``d``; ``need(nchunk)``: elements a tensor must hold from its first for a batch of
     nchunk chunks"""
     what = f"pnp_blend_{layout}"
-    suffix = _blend_entry(what, place, resample, masks.dim(), no_background, src_map, nvar, active, warp)
+    suffix = _blend_entry(what, place, resample, masks.dim(), no_background, src_map, nvar, active, warp, warp_taps)
 
     def call(*args):
         name = f"pnp_blend_scatter_{layout}{suffix}"
@@ -625,15 +643,16 @@ def _pnp_blend(layout, d, x, x2, masks, need, ndst, src_map, nvar, active, place
         return call(nsrc, chunks, int(nvar))
     if suffix == "_variants_sel":
         return call(nsrc, chunks, int(nvar), active)
-    # a table: the _placed / _resampled / _warped entries take the bitmask in every case (all bits: every variant injects)
-    name, table = ("warp", warp) if warp is not None else ("place", place) if place is not None else ("resample", resample)
+    # a table: the _placed / _resampled / _warped / _bilinear entries take the bitmask in every case (all bits: every variant injects)
+    name, table = (("warp_taps", warp_taps) if warp_taps is not None else ("warp", warp) if warp is not None else
+                   ("place", place) if place is not None else ("resample", resample))
     _check_table(what, name, table, masks, nvar, d)
     return call(nsrc, chunks, int(nvar), _all_or(active, nvar), table.data_ptr())
 
 
 def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride, f_stride, p_stride, x2=None,
                      base_chunk0=False, ndst=2, src_map=None, nvar=1, active=None, place=None, no_background=False, resample=None,
-                     warp=None):
+                     warp=None, warp_taps=None):
     """In-place masked blend + scatter on channel-contiguous data (see include/mvoc_hip.h).  ``ndst``: trailing
     destination chunks (2 = [uncond, cond], 1 = [cond] with CFG off).  ``src_map`` = (nsrc, obj_chunks): the batch holds
     nsrc de-duplicated source chunks, object j reads chunk obj_chunks[j] (None: [bg, obj_1..obj_n], the unmapped entry).
@@ -652,7 +671,10 @@ def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride,
     ``warp``: the table of ``warp_table`` for this height x width: every object is read at the pixel its 2-D map
     names (rotation with scale, mirror and translation, nearest), ``masks`` are in destination coordinates -- the ``_warped``
     entry, whatever ``nvar`` / ``src_map`` / ``active`` are.  Not with ``place`` / ``resample``, a per-variant mask stack or
-    ``no_background``."""
+    ``no_background``.
+    ``warp_taps``: the table of ``warp_tap_table`` for this height x width: every object is interpolated from the
+    four pixels its taps name (the same warps, bilinear on an exact fp16 chain) -- the ``_bilinear`` entry, whatever ``nvar`` /
+    ``src_map`` / ``active`` are.  Not with ``place`` / ``resample`` / ``warp``, a per-variant mask stack or ``no_background``."""
     d = _pnp_desc(x, x2, masks, chunk_stride, f_stride, p_stride, frames, height, width, channels, base_chunk0, ndst)
     active = _active_mask(active, nvar, "pnp_blend_tokens")
     if no_background:
@@ -660,6 +682,8 @@ def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride,
             raise RuntimeError("pnp_blend_tokens: no_background with base_chunk0: the base would be the chunk the batch does not hold")
         if warp is not None:
             raise RuntimeError("pnp_blend_tokens: warp= with no_background: pass src_map=(nobj, range(nobj)) instead")
+        if warp_taps is not None:
+            raise RuntimeError("pnp_blend_tokens: warp_taps= with no_background: pass src_map=(nobj, range(nobj)) instead")
         if src_map is not None or nvar != 1 or place is not None or active is not None:
             raise RuntimeError("pnp_blend_tokens: no_background is the positional entry's flag; with a source map, variants or a "
                                "placement pass src_map=(nobj, range(nobj)) instead")
@@ -668,22 +692,22 @@ def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride,
         d.base_chunk0 = -1  # (include/mvoc_hip.h: no background chunk, the base is the last chunk)
     reach = (frames - 1) * f_stride + (height * width - 1) * p_stride + channels  # of the last chunk's last element
     _pnp_blend("tokens", d, x, x2, masks, lambda nchunk: (nchunk - 1) * chunk_stride + reach, ndst, src_map, nvar, active, place,
-               resample, no_background, warp)
+               resample, no_background, warp, warp_taps)
     return x
 
 
 def pnp_blend_nchw(x, masks, *, frames, x2=None, base_chunk0=True, ndst=2, src_map=None, nvar=1, active=None, place=None,
-                   resample=None, warp=None):
+                   resample=None, warp=None, warp_taps=None):
     """In-place on x [(nobj+1+ndst)*F, C, H, W] (reference feature-map layout); with ``src_map`` = (nsrc, obj_chunks)
     x is [(nsrc+ndst)*F, C, H, W], with ``nvar`` = K > 1 [(nsrc+ndst*K)*F, C, H, W]; ``active`` picks the variants that are
-    written, ``place`` moves the objects, ``resample`` scales / mirrors / moves them, ``warp`` also turns them (see
-    ``pnp_blend_tokens``)."""
+    written, ``place`` moves the objects, ``resample`` scales / mirrors / moves them, ``warp`` also turns them, ``warp_taps`` does so
+    with bilinear sampling (see ``pnp_blend_tokens``)."""
     if x.dim() != 4 or not x.is_contiguous():
         raise RuntimeError("pnp_blend_nchw: x must be contiguous [N, C, H, W]")
     d = _pnp_desc(x, x2, masks, 0, 0, 0, frames, x.shape[2], x.shape[3], x.shape[1], base_chunk0, ndst)
     active = _active_mask(active, nvar, "pnp_blend_nchw")
     _pnp_blend("nchw", d, x, x2, masks, lambda nchunk: nchunk * frames * x[0].numel(), ndst, src_map, nvar, active, place, resample,
-               warp=warp)
+               warp=warp, warp_taps=warp_taps)
     return x
 
 
@@ -940,6 +964,159 @@ def warp_planes(src, map, out=None):
         raise RuntimeError("warp_planes: out must be contiguous and of src's shape")
     check(lib.mvoc_gather_planes_warped_f16(src.data_ptr(), out.data_ptr(), src.numel() // (frames * h * w), frames, h, w,
                                             map.data_ptr(), _stream()), "gather_planes_warped")
+    return out
+
+
+# ---- bilinear sampling of warped objects: four taps and fixed-point weights per pixel ------------------------------
+TAP_WEIGHT_ONE = 256  # the weights are q / 256, q an integer in [0, 256]
+TAP_SITE_LIMIT = 65535  # a tap row / column + 1 is a 16-bit field and 0xffff is kept for "absent"
+
+
+def warp_taps_bound(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw):
+    """an upper bound on the magnitude of everything ``level_warp_taps`` forms: with B = ``warp_numerator_bound`` (>= |N| and
+    >= D), |T| = |2N - D| <= 3B, |y0 * 2D| <= |T| + 2D <= 5B and 256 * (T - y0 * 2D) + D < 512D + D = 513D <= 513B -- the factor
+    of 512 the weights add to the nearest rule.  The vectorised int64 form is exact while this stays below 2^62"""
+    return 513 * warp_numerator_bound(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw)
+
+
+def _axis_tap(N, D):
+    T = 2 * N - D                   # the source coordinate minus half a pixel, over 2D
+    i0 = T // (2 * D)               # floor: the upper / left tap
+    q = (TAP_WEIGHT_ONE * (T - i0 * 2 * D) + D) // (2 * D)  # round half up: the weight of tap i0 + 1, 0..256
+    return i0, q
+
+
+def _level_warp_taps_py(dy, dx, myy, myx, mxy, mxx, den, ay2, ax2, H, W, Lh, Lw):
+    dfy, dfx = level_offset(dy, H, Lh), level_offset(dx, W, Lw)
+    cy, cx, Dy, Dx = ay2 * den * H * W, ax2 * den * H * W, 2 * den * W * Lh, 2 * den * H * Lw
+    out = []
+    for iy in range(H):
+        ny = (2 * (iy - dfy) + 1) * Lh - ay2 * H
+        for ix in range(W):
+            nx = (2 * (ix - dfx) + 1) * Lw - ax2 * W
+            y0, qy = _axis_tap(cy + myy * ny * W + myx * nx * H, Dy)
+            x0, qx = _axis_tap(cx + mxy * ny * W + mxx * nx * H, Dx)
+            out.append((y0, x0, qy, qx))
+    return out
+
+
+def _level_warp_taps_i64(dy, dx, myy, myx, mxy, mxx, den, ay2, ax2, H, W, Lh, Lw):
+    """``_level_warp_taps_py`` on int64 tensors (floor division of integers: exact) -- only below ``warp_taps_bound`` 2^62;
+    returns an int64 tensor [H * W, 4]"""
+    dfy, dfx = level_offset(dy, H, Lh), level_offset(dx, W, Lw)
+    ny = ((2 * (torch.arange(H, dtype=torch.int64) - dfy) + 1) * Lh - ay2 * H)[:, None]
+    nx = ((2 * (torch.arange(W, dtype=torch.int64) - dfx) + 1) * Lw - ax2 * W)[None, :]
+    fdiv = lambda a, b: torch.div(a, b, rounding_mode="floor")
+    cols = []
+    for N, D in ((ay2 * den * H * W + myy * W * ny + myx * H * nx, 2 * den * W * Lh),
+                 (ax2 * den * H * W + mxy * W * ny + mxx * H * nx, 2 * den * H * Lw)):
+        T = 2 * N - D
+        i0 = fdiv(T, 2 * D)
+        cols.append((i0, fdiv(TAP_WEIGHT_ONE * (T - i0 * (2 * D)) + D, 2 * D)))
+    (y0, qy), (x0, qx) = cols
+    return torch.stack([y0, x0, qy, qx], dim=-1).reshape(H * W, 4)
+
+
+def _level_warp_taps(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw, form):
+    args = _warp_args(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw)
+    fits = warp_taps_bound(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw) < 2 ** 62
+    if form == "i64" and not fits:
+        raise RuntimeError("level_warp_taps: the int64 form is not exact for these arguments (a term may reach 2^62)")
+    if form not in (None, "py", "i64"):
+        raise RuntimeError(f"level_warp_taps: form {form!r} is not one of None, 'py', 'i64'")
+    return _level_warp_taps_i64(*args) if fits and form != "py" else _level_warp_taps_py(*args)
+
+
+def level_warp_taps(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw, form=None):
+    """the bilinear taps of every destination pixel of an H x W feature grid under an Lh x Lw latent (mask) grid -> a list of
+    H * W tuples (y0, x0, qy, qx).  The arguments and the source coordinate N / D per axis are those of ``level_warp_map`` (which
+    floors it: the nearest pixel); here, per axis,
+        T  = 2N - D                               the coordinate minus half a pixel, over 2D
+        i0 = T // 2D                              the upper / left tap
+        q  = (256 * (T - i0 * 2D) + D) // 2D      round half up: tap i0 + 1 has the weight q / 256, tap i0 the weight (256 - q) / 256
+    Python ints define the rule; the vectorised int64 form is taken only while ``warp_taps_bound`` stays below 2^62 (``form`` =
+    "py" / "i64" forces one: tests).  A pixel is present iff one of its four taps lies inside the plane (``tap_present``)."""
+    out = _level_warp_taps(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw, form)
+    return [tuple(r) for r in out.tolist()] if torch.is_tensor(out) else out
+
+
+def tap_present(y0, x0, H, W):
+    """at least one of the taps (y0, x0), (y0, x0 + 1), (y0 + 1, x0), (y0 + 1, x0 + 1) lies inside the H x W plane; a tap of
+    weight 0 counts"""
+    return -1 <= y0 <= H - 1 and -1 <= x0 <= W - 1
+
+
+def pack_taps(taps, H, W):
+    """(y0, x0, qy, qx) per pixel -> the device form, two int32 words per pixel: word 0 = ((y0 + 1) << 16) | (x0 + 1) (as a signed
+    32-bit value), or -1 where the pixel is absent; word 1 = (qy << 16) | qx"""
+    if H >= TAP_SITE_LIMIT or W >= TAP_SITE_LIMIT:
+        raise RuntimeError(f"pack_taps: {H} x {W}: a site of {TAP_SITE_LIMIT} rows or columns or more does not fit the 16-bit tap fields")
+    out = []
+    for y0, x0, qy, qx in taps:
+        w0 = ((y0 + 1) << 16) | (x0 + 1) if tap_present(y0, x0, H, W) else -1
+        out.append([w0 - (1 << 32) if w0 >= 1 << 31 else w0, (qy << 16) | qx])
+    return out
+
+
+def _level_tap_words(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw):
+    """``pack_taps(level_warp_taps(...))`` as an int32 tensor [H * W, 2], without the detour through lists where the int64 form
+    serves"""
+    t = _level_warp_taps(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw, None)
+    if not torch.is_tensor(t):
+        return torch.tensor(pack_taps(t, H, W), dtype=torch.int32)
+    y0, x0, qy, qx = t.unbind(-1)
+    present = (y0 >= -1) & (y0 <= H - 1) & (x0 >= -1) & (x0 <= W - 1)
+    w0 = torch.where(present, ((y0 + 1) << 16) | (x0 + 1), torch.full_like(y0, -1))
+    w0 = torch.where(w0 >= 1 << 31, w0 - (1 << 32), w0)
+    return torch.stack([w0, (qy << 16) | qx], dim=-1).to(torch.int32)
+
+
+def warp_taps(warp, height, width, mask_h, mask_w):
+    """``warp`` (the value of ``warp_maps``) -> an int32 tensor [nobj, F, height * width, 2] on the CPU: per frame the packed
+    ``level_warp_taps``, computed once per distinct frame value of an object"""
+    if not warp or len({len(w[2]) for w in warp}) != 1 or not warp[0][2]:
+        raise RuntimeError("warp_taps: every object needs the same number (>= 1) of per-frame matrices")
+    if height >= TAP_SITE_LIMIT or width >= TAP_SITE_LIMIT:
+        raise RuntimeError(f"warp_taps: {height} x {width}: a site of {TAP_SITE_LIMIT} rows or columns or more does not fit the "
+                           "16-bit tap fields")
+    rows = []
+    for ay2, ax2, frames in warp:
+        cache = {}
+        obj = []
+        for fr in frames:
+            fr = tuple(fr)
+            if fr not in cache:
+                myy, myx, mxy, mxx, den, dy, dx = fr
+                cache[fr] = _level_tap_words(dy, dx, (myy, myx, mxy, mxx), den, ay2, ax2, height, width, mask_h, mask_w)
+            obj.append(cache[fr])
+        rows.append(torch.stack(obj))
+    return torch.stack(rows).contiguous()
+
+
+def warp_tap_table(warp, height, width, mask_h, mask_w, device):
+    """the device table the ``_bilinear`` blend entries read: int32 [nobj, F, height * width, 2] (``warp_taps``).  The kernels
+    read a tap only inside the plane: every int32 pair is safe to them"""
+    return warp_taps(warp, height, width, mask_h, mask_w).to(device).contiguous()
+
+
+def warp_planes_bilinear(src, taps, out=None):
+    """zero-filled per-frame bilinear gather of contiguous fp16 planes [..., F, h, w] (leading dims = planes of ONE object)
+    through a tap table: out[.., f, pix] = the fp16 chain of DESIGN.md 6r on the four taps of taps_f[pix], 0 where none lies
+    inside.  ``taps``: device int32 [F, h * w, 2]."""
+    _chk(src, "src"), _chk(taps, "taps", torch.int32)
+    if src.dim() < 3 or not src.is_contiguous():
+        raise RuntimeError(f"warp_planes_bilinear: src must be contiguous [..., F, h, w], got {tuple(src.shape)}")
+    frames, h, w = src.shape[-3:]
+    if tuple(taps.shape) != (frames, h * w, 2) or not taps.is_contiguous():
+        raise RuntimeError(f"warp_planes_bilinear: taps must be a contiguous int32 [F = {frames}, h * w = {h * w}, 2] table, got "
+                           f"{tuple(taps.shape)}")
+    if out is None:
+        out = torch.empty_like(src)
+    _chk(out, "out")
+    if out.shape != src.shape or not out.is_contiguous():
+        raise RuntimeError("warp_planes_bilinear: out must be contiguous and of src's shape")
+    check(lib.mvoc_gather_planes_bilinear_f16(src.data_ptr(), out.data_ptr(), src.numel() // (frames * h * w), frames, h, w,
+                                              taps.data_ptr(), _stream()), "gather_planes_bilinear")
     return out
 
 

@@ -744,6 +744,14 @@ class I2VGenXLUNet:
         # frame f at the pixel its 2-D map names (ops.level_warp_map for the site's H x W) through the _warped blend entries; the
         # hook masks are in destination coordinates already (the pipeline gathers them once per call).  Shared by the variants.
         self.warp = None
+        # Bilinear sampling of the warp (pipeline.py obj_transform_filter): None = nearest (the _warped entries,
+        # today's calls) or "bilinear": every injection site then interpolates object j of frame f from the four pixels its taps
+        # name (ops.level_warp_taps for the site's H x W) through the _bilinear blend entries.  A property of the ``warp`` mode, not
+        # a mode: meaningful only while ``warp`` is set (a site refuses it otherwise); frame shard, mixes and object counts are
+        # refused as for the warp.  The tap tables have a cache of their own, (warp, {(H, W, mh, mw): table}): _level_tables["warp"]
+        # holds nearest tables only.
+        self.warp_filter = None
+        self._tap_tables = (None, {})
         # the modes' device tables: attribute name -> (value, {(H, W, mh, mw): table}); a mode's tables are dropped when ITS value
         # changes, so states of different modes that step alternately keep theirs
         self._level_tables = {m.attr: (None, {}) for m in PLACEMENT_MODES}
@@ -980,9 +988,22 @@ class I2VGenXLUNet:
         """keyword arguments of a site's blend call: none without a placement or transform (exactly today's call), else
         ``place=`` -- or, under ``transform`` / ``variant_transforms``, ``resample=``, under ``warp``, ``warp=`` -- the level's
         device table: [nobj, F, 2] offsets, [nobj, F, H + W] per-axis index maps (a leading K in the per-variant modes) or the
-        [nobj, F, H * W] 2-D index map.  Built once per (value, H, W,
-        mh, mw) and dropped when the mode's value changes"""
+        [nobj, F, H * W] 2-D index map; under ``warp`` with ``warp_filter`` = "bilinear", ``warp_taps=`` the [nobj, F, H * W, 2] tap
+        table.  Built once per (value, H, W, mh, mw) and dropped when the mode's value changes"""
         m = self._placement_mode(mask_list)
+        if self.warp_filter is not None:
+            if self.warp_filter != "bilinear":
+                raise RuntimeError(f"warp_filter is {self.warp_filter!r}: None (nearest) or 'bilinear'")
+            if m is None or m.attr != "warp":
+                raise RuntimeError("warp_filter is set but warp is not: the filter is a property of the warp mode (resolve the call's "
+                                   "transforms to a warp, or leave the filter None)")
+            if self._tap_tables[0] != self.warp:
+                self._tap_tables = (self.warp, {})
+            mh, mw = self._all_frame_masks(mask_list)[0].shape[2:]
+            key = (H, W, mh, mw)
+            if key not in self._tap_tables[1]:
+                self._tap_tables[1][key] = ops.warp_tap_table(self.warp, H, W, mh, mw, self.device)
+            return {"warp_taps": self._tap_tables[1][key]}
         if m is None:
             return {}
         value = getattr(self, m.attr)

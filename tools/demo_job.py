@@ -29,6 +29,8 @@ of source chunks.  With --sequential the K single jobs each take their variant's
 --variant-transform "scale=3/2,flip=h;scale=1/2||offset=64,0;" (opt-in, needs --variants K): K transforms separated by `|`, each
 in the format of --transform -- the variants' `transform` key; an empty item leaves that variant untransformed.
 With --sequential the K single jobs each take their variant's transform as `obj_transform`.
+--transform-filter bilinear (opt-in, needs --transform): the entry's `obj_transform_filter` -- scaled, mirrored and
+turned objects are sampled bilinearly; the result line then names the filter (`obj_transform_filter`).  Not with --variant-transform.
 
 --shared-source (opt-in): the shape of MVOC's own demo entries, where the background and both objects point at ONE inversion
 directory and the same control frames.  One clip is inverted, then the composition runs with source de-duplication off and then
@@ -450,10 +452,16 @@ def parse_variant_transform(text, variants):
 
 
 def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, thresholds=None, sequential=False, place=None,
-                 variant_place=None, transform=None, variant_transform=None):
+                 variant_place=None, transform=None, variant_transform=None, transform_filter=None):
     """K prompts and seeds over the boat_surf-shaped job (three distinct sources), one composition loop (composite.py `variants`).
     ``thresholds``: K values of pnp_spatial_attn_t, one per variant (the variants' `pnp` key); ``sequential``: after
     the one loop, the same K compositions one by one (single entries with the flat threshold) for the comparison."""
+    if transform_filter is not None:  # refused before any work is done
+        if transform is None:
+            raise SystemExit("--transform-filter needs --transform (the filter samples the entry's transformed objects)")
+        if variant_transform is not None and transform_filter == "bilinear":
+            raise SystemExit("--transform-filter bilinear does not combine with --variant-transform: one filter samples the objects "
+                             "of --transform for all variants")
     composite, inverse, _ = _import_drivers()
     from mvoc_amd.config import OmegaConf
     from mvoc_amd import pipeline as pl
@@ -498,6 +506,8 @@ def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, threshol
         centry["obj_offset"] = [list(p) for p in place]
     if transform is not None:  # scale / mirror / offset per object: an entry key, shared by the variants
         centry["obj_transform"] = [dict(t) for t in transform]
+    if transform_filter is not None:  # how the transformed objects are sampled: an entry key next to obj_transform
+        centry["obj_transform_filter"] = transform_filter
     with StageTimer(pl) as timer:
         composite.main(ct, [centry], dev, synthetic=True)
     res = timer.result()
@@ -514,6 +524,8 @@ def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, threshol
         res["variant_placement"] = [[list(q) for q in p] for p in variant_place]
     if transform is not None:
         res["obj_transform"] = [dict(t) for t in transform]
+        if transform_filter is not None:  # (without the option the result line is the one of a run before the option existed)
+            res["obj_transform_filter"] = transform_filter
     if variant_transform is not None:
         res["variant_transform"] = [None if t is None else [dict(o) for o in t] for t in variant_transform]
     if thresholds is not None:
@@ -530,6 +542,8 @@ def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, threshol
                 e["obj_offset"] = [list(q) for q in variant_place[k]]
             if transform is not None:
                 e["obj_transform"] = [dict(t) for t in transform]
+                if transform_filter is not None:
+                    e["obj_transform_filter"] = transform_filter
             if variant_transform is not None and variant_transform[k] is not None:  # the single job of variant k: its transform as the entry's
                 e["obj_transform"] = [dict(o) for o in variant_transform[k]]
             if thresholds is not None:
@@ -576,16 +590,18 @@ if __name__ == "__main__":
     ap.add_argument("--variant-transform", type=str, default=None, metavar="scale=p/q,flip=h;..|..",
                     help="with --variants K: K transforms separated by |, each in the format of --transform (the variants' "
                          "`transform` key); an empty item leaves that variant untransformed")
+    ap.add_argument("--transform-filter", type=str, default=None, choices=("nearest", "bilinear"),
+                    help="with --transform: how the transformed objects are sampled (`obj_transform_filter`; default nearest)")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
-    if a.variants or a.place or a.variant_place or a.transform or a.variant_transform:
+    if a.variants or a.place or a.variant_place or a.transform or a.variant_transform or a.transform_filter:
         th = None if a.variant_thresholds is None else [float(x) for x in a.variant_thresholds.split(",")]
         place = None if a.place is None else parse_place(a.place)
         vplace = None if a.variant_place is None else parse_variant_place(a.variant_place, a.variants)
         transform = None if a.transform is None else parse_transform(a.transform)
         vtransform = None if a.variant_transform is None else parse_variant_transform(a.variant_transform, a.variants)
         print(json.dumps(run_variants(a.frames, a.size, a.steps, a.keep, a.variants or 1, th, a.sequential, place, vplace, transform,
-                                      vtransform)), flush=True)
+                                      vtransform, a.transform_filter)), flush=True)
     else:
         fn = run_shared_source if a.shared_source else run
         print(json.dumps(fn(a.frames, a.size, a.steps, a.keep)), flush=True)
