@@ -7,8 +7,9 @@
 // write 2 destination chunks, for Q and K = 10 x 41.9 MB + masks (1 fp16 per (frame, pixel), never expanded to
 // [F,H,W,C]) = 419.6 MB -- the reference moves several times that through rearrange/repeat copies.
 //
-// The argument block, the pieces of the blend-scatter family and its host launch path are in pnp_blend.h (shared with
-// pnp_variants2.hip).
+// The argument block, the pieces of the blend-scatter family, its table forms and the one host body of its variant entries
+// (run_entry) and of the plane movers (move_planes) are in pnp_blend.h, shared with pnp_variants2.hip, pnp_warp.hip and
+// pnp_bilinear.hip.
 #include "pnp_blend.h"
 
 namespace {
@@ -317,195 +318,103 @@ int launch_nchw(const mvoc_pnp_desc* d, PnpArgs& a, int nread, void* stream) {
   return mvoc_check_launch("pnp_nchw_kernel");
 }
 
-// variants: every variant injects (an nvar outside [1, 8] is refused before the mask is looked at)
-int fill_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar, PnpArgs& a, double& chunks) {
-  return fill_variants_sel(d, nsrc, obj_chunk, nvar, nvar >= 1 && nvar <= 8 ? (1u << nvar) - 1 : 0u, a, chunks);
-}
-
-// _resampled: the _placed contract with the table of per-axis index maps in place of the offset table
-int fill_resampled(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar, uint32_t active, const void* maps,
-                   PnpArgs& a, double& chunks) {
-  MVOC_REQUIRE(maps, -1, "pnp resampled: null map table");
-  return fill_variants_sel(d, nsrc, obj_chunk, nvar, active, a, chunks);
-}
-
 }  // namespace
 
+// Every entry below is run_entry (pnp_blend.h) on its table form, its layout's prepare_* and the launch of its own kernel.
 extern "C" int mvoc_pnp_blend_scatter_tokens_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
                                                       int32_t nvar, void* stream) {
-  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_tokens_variants")) return rc;
-  PnpArgs a;
-  Launch l;
-  double chunks = 0;
-  if (int rc = fill_variants(d, nsrc, obj_chunk, nvar, a, chunks)) return rc;
-  if (int rc = prepare_tokens(d, a, stream, l)) return rc;
-  MvocProfScope prof(MVOC_FAM_PNP, l.s, blend_bytes(l, d->nobj, chunks));
-  dispatch(d->nobj, l.vec, [&](auto n, auto) { launch(pnp_tokens_variants_kernel<n.value>, l, a, (int)nvar); });
-  return mvoc_check_launch("pnp_tokens_variants_kernel");
+  return run_entry("mvoc_pnp_blend_scatter_tokens_variants", "pnp_tokens_variants_kernel", NO_TABLE, prepare_tokens, d, nsrc, obj_chunk,
+                   nvar, all_variants(nvar), nullptr, stream, [&](auto n, auto, const Launch& l, const PnpArgs& a) {
+                     launch(pnp_tokens_variants_kernel<n.value>, l, a, (int)nvar);
+                   });
 }
 
 extern "C" int mvoc_pnp_blend_scatter_nchw_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
                                                     int32_t nvar, void* stream) {
-  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_nchw_variants")) return rc;
-  PnpArgs a;
-  Launch l;
-  double chunks = 0;
-  if (int rc = fill_variants(d, nsrc, obj_chunk, nvar, a, chunks)) return rc;
-  if (int rc = prepare_nchw(d, a, stream, l)) return rc;
-  MvocProfScope prof(MVOC_FAM_PNP, l.s, blend_bytes(l, d->nobj, chunks));
-  dispatch(d->nobj, l.vec, [&](auto n, auto v) { launch(pnp_nchw_variants_kernel<v.value, n.value>, l, a, (int)nvar); });
-  return mvoc_check_launch("pnp_nchw_variants_kernel");
+  return run_entry("mvoc_pnp_blend_scatter_nchw_variants", "pnp_nchw_variants_kernel", NO_TABLE, prepare_nchw, d, nsrc, obj_chunk, nvar,
+                   all_variants(nvar), nullptr, stream, [&](auto n, auto v, const Launch& l, const PnpArgs& a) {
+                     launch(pnp_nchw_variants_kernel<v.value, n.value>, l, a, (int)nvar);
+                   });
 }
 
 extern "C" int mvoc_pnp_blend_scatter_tokens_variants_sel(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
                                                           int32_t nvar, uint32_t active, void* stream) {
-  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_tokens_variants_sel")) return rc;
-  PnpArgs a;
-  Launch l;
-  double chunks = 0;
-  if (int rc = fill_variants_sel(d, nsrc, obj_chunk, nvar, active, a, chunks)) return rc;
-  if (int rc = prepare_tokens(d, a, stream, l)) return rc;
-  MvocProfScope prof(MVOC_FAM_PNP, l.s, blend_bytes(l, d->nobj, chunks));
-  dispatch(d->nobj, l.vec, [&](auto n, auto) { launch(pnp_tokens_variants_sel_kernel<n.value>, l, a, (int)nvar, (unsigned)active); });
-  return mvoc_check_launch("pnp_tokens_variants_sel_kernel");
+  return run_entry("mvoc_pnp_blend_scatter_tokens_variants_sel", "pnp_tokens_variants_sel_kernel", NO_TABLE, prepare_tokens, d, nsrc,
+                   obj_chunk, nvar, active, nullptr, stream, [&](auto n, auto, const Launch& l, const PnpArgs& a) {
+                     launch(pnp_tokens_variants_sel_kernel<n.value>, l, a, (int)nvar, (unsigned)active);
+                   });
 }
 
 extern "C" int mvoc_pnp_blend_scatter_nchw_variants_sel(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
                                                         int32_t nvar, uint32_t active, void* stream) {
-  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_nchw_variants_sel")) return rc;
-  PnpArgs a;
-  Launch l;
-  double chunks = 0;
-  if (int rc = fill_variants_sel(d, nsrc, obj_chunk, nvar, active, a, chunks)) return rc;
-  if (int rc = prepare_nchw(d, a, stream, l)) return rc;
-  MvocProfScope prof(MVOC_FAM_PNP, l.s, blend_bytes(l, d->nobj, chunks));
-  dispatch(d->nobj, l.vec,
-           [&](auto n, auto v) { launch(pnp_nchw_variants_sel_kernel<v.value, n.value>, l, a, (int)nvar, (unsigned)active); });
-  return mvoc_check_launch("pnp_nchw_variants_sel_kernel");
+  return run_entry("mvoc_pnp_blend_scatter_nchw_variants_sel", "pnp_nchw_variants_sel_kernel", NO_TABLE, prepare_nchw, d, nsrc, obj_chunk,
+                   nvar, active, nullptr, stream, [&](auto n, auto v, const Launch& l, const PnpArgs& a) {
+                     launch(pnp_nchw_variants_sel_kernel<v.value, n.value>, l, a, (int)nvar, (unsigned)active);
+                   });
 }
 
 extern "C" int mvoc_pnp_blend_scatter_tokens_placed(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
                                                     uint32_t active, const int32_t* place, void* stream) {
-  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_tokens_placed")) return rc;
-  PnpArgs a;
-  Launch l;
-  double chunks = 0;
-  if (int rc = fill_placed(d, nsrc, obj_chunk, nvar, active, place, a, chunks)) return rc;
-  if (int rc = prepare_tokens(d, a, stream, l)) return rc;
-  MvocProfScope prof(MVOC_FAM_PNP, l.s, blend_bytes(l, d->nobj, chunks));
-  dispatch(d->nobj, l.vec, [&](auto n, auto) {
-    launch(pnp_tokens_placed_kernel<n.value>, l, a, (int)nvar, (unsigned)active, (const int*)place);
-  });
-  return mvoc_check_launch("pnp_tokens_placed_kernel");
+  return run_entry("mvoc_pnp_blend_scatter_tokens_placed", "pnp_tokens_placed_kernel", PLACED, prepare_tokens, d, nsrc, obj_chunk, nvar,
+                   active, place, stream, [&](auto n, auto, const Launch& l, const PnpArgs& a) {
+                     launch(pnp_tokens_placed_kernel<n.value>, l, a, (int)nvar, (unsigned)active, (const int*)place);
+                   });
 }
 
 extern "C" int mvoc_pnp_blend_scatter_nchw_placed(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
                                                   uint32_t active, const int32_t* place, void* stream) {
-  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_nchw_placed")) return rc;
-  PnpArgs a;
-  Launch l;
-  double chunks = 0;
-  if (int rc = fill_placed(d, nsrc, obj_chunk, nvar, active, place, a, chunks)) return rc;
-  if (int rc = prepare_nchw(d, a, stream, l)) return rc;
-  MvocProfScope prof(MVOC_FAM_PNP, l.s, blend_bytes(l, d->nobj, chunks));
-  dispatch(d->nobj, l.vec, [&](auto n, auto v) {
-    launch(pnp_nchw_placed_kernel<v.value, n.value>, l, a, (int)nvar, (unsigned)active, (const int*)place);
-  });
-  return mvoc_check_launch("pnp_nchw_placed_kernel");
+  return run_entry("mvoc_pnp_blend_scatter_nchw_placed", "pnp_nchw_placed_kernel", PLACED, prepare_nchw, d, nsrc, obj_chunk, nvar, active,
+                   place, stream, [&](auto n, auto v, const Launch& l, const PnpArgs& a) {
+                     launch(pnp_nchw_placed_kernel<v.value, n.value>, l, a, (int)nvar, (unsigned)active, (const int*)place);
+                   });
 }
 
 extern "C" int mvoc_pnp_blend_scatter_tokens_placed_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
                                                              int32_t nvar, uint32_t active, const int32_t* place, void* stream) {
-  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_tokens_placed_variants")) return rc;
-  PnpArgs a;
-  Launch l;
-  double chunks = 0;
-  int on = 0;
-  if (int rc = fill_placed_variants(d, nsrc, obj_chunk, nvar, active, place, a, chunks, on)) return rc;
-  if (int rc = prepare_tokens(d, a, stream, l)) return rc;
-  MvocProfScope prof(MVOC_FAM_PNP, l.s, blend_bytes(l, d->nobj, chunks, on, 8.0 * nvar * d->nobj * d->frames));
-  dispatch(d->nobj, l.vec, [&](auto n, auto) {
-    launch(pnp_tokens_placed_variants_kernel<n.value>, l, a, (int)nvar, (unsigned)active, (const int*)place);
-  });
-  return mvoc_check_launch("pnp_tokens_placed_variants_kernel");
+  return run_entry("mvoc_pnp_blend_scatter_tokens_placed_variants", "pnp_tokens_placed_variants_kernel", PLACED_VARIANTS, prepare_tokens,
+                   d, nsrc, obj_chunk, nvar, active, place, stream, [&](auto n, auto, const Launch& l, const PnpArgs& a) {
+                     launch(pnp_tokens_placed_variants_kernel<n.value>, l, a, (int)nvar, (unsigned)active, (const int*)place);
+                   });
 }
 
 extern "C" int mvoc_pnp_blend_scatter_nchw_placed_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk,
                                                            int32_t nvar, uint32_t active, const int32_t* place, void* stream) {
-  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_nchw_placed_variants")) return rc;
-  PnpArgs a;
-  Launch l;
-  double chunks = 0;
-  int on = 0;
-  if (int rc = fill_placed_variants(d, nsrc, obj_chunk, nvar, active, place, a, chunks, on)) return rc;
-  if (int rc = prepare_nchw(d, a, stream, l)) return rc;
-  MvocProfScope prof(MVOC_FAM_PNP, l.s, blend_bytes(l, d->nobj, chunks, on, 8.0 * nvar * d->nobj * d->frames));
-  dispatch(d->nobj, l.vec, [&](auto n, auto v) {
-    launch(pnp_nchw_placed_variants_kernel<v.value, n.value>, l, a, (int)nvar, (unsigned)active, (const int*)place);
-  });
-  return mvoc_check_launch("pnp_nchw_placed_variants_kernel");
+  return run_entry("mvoc_pnp_blend_scatter_nchw_placed_variants", "pnp_nchw_placed_variants_kernel", PLACED_VARIANTS, prepare_nchw, d,
+                   nsrc, obj_chunk, nvar, active, place, stream, [&](auto n, auto v, const Launch& l, const PnpArgs& a) {
+                     launch(pnp_nchw_placed_variants_kernel<v.value, n.value>, l, a, (int)nvar, (unsigned)active, (const int*)place);
+                   });
 }
 
 extern "C" int mvoc_pnp_blend_scatter_tokens_resampled(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
                                                        uint32_t active, const int32_t* maps, void* stream) {
-  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_tokens_resampled")) return rc;
-  PnpArgs a;
-  Launch l;
-  double chunks = 0;
-  if (int rc = fill_resampled(d, nsrc, obj_chunk, nvar, active, maps, a, chunks)) return rc;
-  if (int rc = prepare_tokens(d, a, stream, l)) return rc;
-  MvocProfScope prof(MVOC_FAM_PNP, l.s,
-                     blend_bytes(l, d->nobj, chunks, 1.0, 4.0 * d->nobj * d->frames * ((double)d->height + d->width)));
-  dispatch(d->nobj, l.vec, [&](auto n, auto) {
-    launch(pnp_tokens_resampled_kernel<n.value>, l, a, (int)nvar, (unsigned)active, (const int*)maps);
-  });
-  return mvoc_check_launch("pnp_tokens_resampled_kernel");
+  return run_entry("mvoc_pnp_blend_scatter_tokens_resampled", "pnp_tokens_resampled_kernel", RESAMPLED, prepare_tokens, d, nsrc,
+                   obj_chunk, nvar, active, maps, stream, [&](auto n, auto, const Launch& l, const PnpArgs& a) {
+                     launch(pnp_tokens_resampled_kernel<n.value>, l, a, (int)nvar, (unsigned)active, (const int*)maps);
+                   });
 }
 
 extern "C" int mvoc_pnp_blend_scatter_nchw_resampled(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
                                                      uint32_t active, const int32_t* maps, void* stream) {
-  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_nchw_resampled")) return rc;
-  PnpArgs a;
-  Launch l;
-  double chunks = 0;
-  if (int rc = fill_resampled(d, nsrc, obj_chunk, nvar, active, maps, a, chunks)) return rc;
-  if (int rc = prepare_nchw(d, a, stream, l)) return rc;
-  MvocProfScope prof(MVOC_FAM_PNP, l.s,
-                     blend_bytes(l, d->nobj, chunks, 1.0, 4.0 * d->nobj * d->frames * ((double)d->height + d->width)));
-  dispatch(d->nobj, l.vec, [&](auto n, auto v) {
-    launch(pnp_nchw_resampled_kernel<v.value, n.value>, l, a, (int)nvar, (unsigned)active, (const int*)maps);
-  });
-  return mvoc_check_launch("pnp_nchw_resampled_kernel");
+  return run_entry("mvoc_pnp_blend_scatter_nchw_resampled", "pnp_nchw_resampled_kernel", RESAMPLED, prepare_nchw, d, nsrc, obj_chunk,
+                   nvar, active, maps, stream, [&](auto n, auto v, const Launch& l, const PnpArgs& a) {
+                     launch(pnp_nchw_resampled_kernel<v.value, n.value>, l, a, (int)nvar, (unsigned)active, (const int*)maps);
+                   });
 }
 
 extern "C" int mvoc_gather_planes_f16(const void* src, void* dst, int32_t nplane, int32_t frames, int32_t h, int32_t w,
                                       const int32_t* maps, void* stream) {
-  MVOC_REQUIRE(src && dst && maps, -1, "gather_planes: null operand");
-  MVOC_REQUIRE(src != dst, -1, "gather_planes: in place (src == dst) is not supported");
-  MVOC_REQUIRE(nplane > 0 && frames > 0 && h > 0 && w > 0, -1, "gather_planes: bad dims");
-  const long n = (long)nplane * frames * h * w;
-  const long nblk = (n + 255) / 256;
-  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "gather_planes: grid too large");
-  hipStream_t s = (hipStream_t)stream;
-  MvocProfScope prof(MVOC_FAM_MISC, s, 2.0 * n * 2 + 4.0 * frames * ((double)h + w));
-  hipLaunchKernelGGL(gather_planes_kernel, dim3((unsigned)nblk), dim3(256), 0, s, (const half_t*)src, (half_t*)dst, (int)frames,
-                     (int)h, (int)w, (const int*)maps, n);
-  return mvoc_check_launch("gather_planes_kernel");
+  return move_planes(RESAMPLED, "gather_planes_kernel", src, dst, nplane, frames, h, w, maps, stream, [&](dim3 grid, hipStream_t s, long n) {
+    hipLaunchKernelGGL(gather_planes_kernel, grid, dim3(256), 0, s, (const half_t*)src, (half_t*)dst, (int)frames, (int)h, (int)w,
+                       (const int*)maps, n);
+  });
 }
 
 extern "C" int mvoc_shift_planes_f16(const void* src, void* dst, int32_t nplane, int32_t frames, int32_t h, int32_t w,
                                      const int32_t* offsets, void* stream) {
-  MVOC_REQUIRE(src && dst && offsets, -1, "shift_planes: null operand");
-  MVOC_REQUIRE(src != dst, -1, "shift_planes: in place (src == dst) is not supported");
-  MVOC_REQUIRE(nplane > 0 && frames > 0 && h > 0 && w > 0, -1, "shift_planes: bad dims");
-  const long n = (long)nplane * frames * h * w;
-  const long nblk = (n + 255) / 256;
-  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "shift_planes: grid too large");
-  hipStream_t s = (hipStream_t)stream;
-  MvocProfScope prof(MVOC_FAM_MISC, s, 2.0 * n * 2);
-  hipLaunchKernelGGL(shift_planes_kernel, dim3((unsigned)nblk), dim3(256), 0, s, (const half_t*)src, (half_t*)dst, (int)frames,
-                     (int)h, (int)w, (const int*)offsets, n);
-  return mvoc_check_launch("shift_planes_kernel");
+  return move_planes(PLACED, "shift_planes_kernel", src, dst, nplane, frames, h, w, offsets, stream, [&](dim3 grid, hipStream_t s, long n) {
+    hipLaunchKernelGGL(shift_planes_kernel, grid, dim3(256), 0, s, (const half_t*)src, (half_t*)dst, (int)frames, (int)h, (int)w,
+                       (const int*)offsets, n);
+  });
 }
 
 extern "C" int mvoc_ddim_step_variants_f16(const void* x, const void* v_uncond, const void* v_cond, const float* coef_dev,

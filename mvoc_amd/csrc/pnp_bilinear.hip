@@ -4,6 +4,8 @@
 // the chunks hold the bits the unplaced entries write on sources that were interpolated beforehand by the same chain.  The
 // kernels are blend_scatter<L, TAPS, true, NOBJ> composed from the pieces of pnp_blend.h exactly as pnp_warp.hip composes its
 // MAP2 kernels.  A translation unit of its own: the kernel census of pnp.o, pnp_variants2.o and pnp_warp.o is pinned by tests.
+// It holds the kernels and one call per entry: the form's row (BILINEAR) and the bodies of the entries and of the mover (run_entry,
+// move_planes) are in pnp_blend.h, as for pnp.hip, pnp_variants2.hip and pnp_warp.hip.
 //
 // Bytes reported to the profiler (MvocProfScope): those of the _warped entries with the table term 8 * nobj * F * H * W -- every
 // DISTINCT object chunk is counted once although a destination pixel reads up to four of its pixels (neighbouring destinations
@@ -44,65 +46,31 @@ __global__ __launch_bounds__(256) void gather_planes_bilinear_kernel(const half_
   dst[i] = taps_value(t, v[0], v[1], v[2], v[3]);
 }
 
-// _bilinear: the _warped contract with the tap table in place of the 2-D map.  A tap row / column + 1 is a 16-bit field of word 0
-// and 0xffff is kept for "absent": a site with 65 535 rows or columns or more is refused
-int fill_bilinear(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar, uint32_t active, const void* taps,
-                  PnpArgs& a, double& chunks) {
-  MVOC_REQUIRE(taps, -1, "pnp bilinear: null tap table");
-  if (int rc = fill_variants_sel(d, nsrc, obj_chunk, nvar, active, a, chunks)) return rc;
-  MVOC_REQUIRE((long)d->height * d->width < 0x7fffffffL, -2, "pnp bilinear: height * width does not fit an int");
-  MVOC_REQUIRE(d->height < 65535 && d->width < 65535, -2,
-               "pnp bilinear: height %d or width %d does not fit the 16-bit tap fields (< 65535)", d->height, d->width);
-  return 0;
-}
-
-double table_bytes(const mvoc_pnp_desc* d) { return 8.0 * d->nobj * d->frames * (double)d->height * d->width; }
-
 }  // namespace
 
+// run_entry / move_planes (pnp_blend.h) on the BILINEAR form: the _warped contract with the tap table in place of the 2-D map,
+// and the form's limits on height * width and on the 16-bit tap fields
 extern "C" int mvoc_pnp_blend_scatter_tokens_bilinear(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
                                                       uint32_t active, const int32_t* taps, void* stream) {
-  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_tokens_bilinear")) return rc;
-  PnpArgs a;
-  Launch l;
-  double chunks = 0;
-  if (int rc = fill_bilinear(d, nsrc, obj_chunk, nvar, active, taps, a, chunks)) return rc;
-  if (int rc = prepare_tokens(d, a, stream, l)) return rc;
-  MvocProfScope prof(MVOC_FAM_PNP, l.s, blend_bytes(l, d->nobj, chunks, 1.0, table_bytes(d)));
-  dispatch(d->nobj, l.vec, [&](auto n, auto) {
-    launch(pnp_tokens_bilinear_kernel<n.value>, l, a, (int)nvar, (unsigned)active, (const int*)taps);
-  });
-  return mvoc_check_launch("pnp_tokens_bilinear_kernel");
+  return run_entry("mvoc_pnp_blend_scatter_tokens_bilinear", "pnp_tokens_bilinear_kernel", BILINEAR, prepare_tokens, d, nsrc, obj_chunk,
+                   nvar, active, taps, stream, [&](auto n, auto, const Launch& l, const PnpArgs& a) {
+                     launch(pnp_tokens_bilinear_kernel<n.value>, l, a, (int)nvar, (unsigned)active, (const int*)taps);
+                   });
 }
 
 extern "C" int mvoc_pnp_blend_scatter_nchw_bilinear(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar,
                                                     uint32_t active, const int32_t* taps, void* stream) {
-  if (int rc = refuse_no_background(d, "mvoc_pnp_blend_scatter_nchw_bilinear")) return rc;
-  PnpArgs a;
-  Launch l;
-  double chunks = 0;
-  if (int rc = fill_bilinear(d, nsrc, obj_chunk, nvar, active, taps, a, chunks)) return rc;
-  if (int rc = prepare_nchw(d, a, stream, l)) return rc;
-  MvocProfScope prof(MVOC_FAM_PNP, l.s, blend_bytes(l, d->nobj, chunks, 1.0, table_bytes(d)));
-  dispatch(d->nobj, l.vec, [&](auto n, auto v) {
-    launch(pnp_nchw_bilinear_kernel<v.value, n.value>, l, a, (int)nvar, (unsigned)active, (const int*)taps);
-  });
-  return mvoc_check_launch("pnp_nchw_bilinear_kernel");
+  return run_entry("mvoc_pnp_blend_scatter_nchw_bilinear", "pnp_nchw_bilinear_kernel", BILINEAR, prepare_nchw, d, nsrc, obj_chunk, nvar,
+                   active, taps, stream, [&](auto n, auto v, const Launch& l, const PnpArgs& a) {
+                     launch(pnp_nchw_bilinear_kernel<v.value, n.value>, l, a, (int)nvar, (unsigned)active, (const int*)taps);
+                   });
 }
 
 extern "C" int mvoc_gather_planes_bilinear_f16(const void* src, void* dst, int32_t nplane, int32_t frames, int32_t h, int32_t w,
                                                const int32_t* taps, void* stream) {
-  MVOC_REQUIRE(src && dst && taps, -1, "gather_planes_bilinear: null operand");
-  MVOC_REQUIRE(src != dst, -1, "gather_planes_bilinear: in place (src == dst) is not supported");
-  MVOC_REQUIRE(nplane > 0 && frames > 0 && h > 0 && w > 0, -1, "gather_planes_bilinear: bad dims");
-  MVOC_REQUIRE((long)h * w < 0x7fffffffL, -2, "gather_planes_bilinear: h * w does not fit an int");
-  MVOC_REQUIRE(h < 65535 && w < 65535, -2, "gather_planes_bilinear: h %d or w %d does not fit the 16-bit tap fields (< 65535)", h, w);
-  const long n = (long)nplane * frames * h * w;
-  const long nblk = (n + 255) / 256;
-  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "gather_planes_bilinear: grid too large");
-  hipStream_t s = (hipStream_t)stream;
-  MvocProfScope prof(MVOC_FAM_MISC, s, 2.0 * n * 2 + 8.0 * frames * (double)h * w);
-  hipLaunchKernelGGL(gather_planes_bilinear_kernel, dim3((unsigned)nblk), dim3(256), 0, s, (const half_t*)src, (half_t*)dst,
-                     (int)frames, (int)h, (int)w, (const int*)taps, n);
-  return mvoc_check_launch("gather_planes_bilinear_kernel");
+  return move_planes(BILINEAR, "gather_planes_bilinear_kernel", src, dst, nplane, frames, h, w, taps, stream,
+                     [&](dim3 grid, hipStream_t s, long n) {
+                       hipLaunchKernelGGL(gather_planes_bilinear_kernel, grid, dim3(256), 0, s, (const half_t*)src, (half_t*)dst,
+                                          (int)frames, (int)h, (int)w, (const int*)taps, n);
+                     });
 }

@@ -1,9 +1,11 @@
 // The pieces of the blend-scatter family that more than one translation unit composes its kernels
 // from: the argument block and what fills / refuses it, the fp16 blend, the two item geometries with their object loads, the
-// per-variant scatter and the host launch path.  pnp.hip holds the family's ten kernels (and the text that describes the
-// pieces); pnp_variants2.hip the per-variant MAP form; pnp_warp.hip the MAP2 form (a 2-D index map: rotation);
-// pnp_bilinear.hip the TAPS form (four taps and fixed-point weights per pixel: bilinear sampling).
-// Everything is in an anonymous namespace: each unit gets its own copy.
+// per-variant scatter and the host path: the table forms (one row each), run_entry (the one body of every entry that takes
+// variants), move_planes (the one body of the plane movers) and what they launch through.  pnp.hip holds the
+// family's ten kernels (and the text that describes the pieces), the two nearest plane movers and their entries;
+// pnp_variants2.hip the per-variant MAP form; pnp_warp.hip the MAP2 form (a 2-D index map: rotation);
+// pnp_bilinear.hip the TAPS form (four taps and fixed-point weights per pixel: bilinear sampling) -- each unit its
+// kernels and one call per entry.  Everything is in an anonymous namespace: each unit gets its own copy.
 #pragma once
 #include <type_traits>
 
@@ -489,24 +491,56 @@ int fill_variants_sel(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_c
   return 0;
 }
 
-// _placed: the _sel contract (nvar = 1 and every bit of `active` set are allowed) + the device table of feature offsets
-int fill_placed(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar, uint32_t active, const void* place,
-                PnpArgs& a, double& chunks) {
-  MVOC_REQUIRE(place, -1, "pnp placed: null offset table");
-  return fill_variants_sel(d, nsrc, obj_chunk, nvar, active, a, chunks);
+// `active` of the entries without one: every variant injects (an nvar outside [1, 8] is refused before the mask is looked at)
+uint32_t all_variants(int32_t nvar) { return nvar >= 1 && nvar <= 8 ? (1u << nvar) - 1 : 0u; }
+
+// ---- host: the table forms ----------------------------------------------------------------------------------------------------
+// A table form is what an entry adds to the _sel contract (nvar = 1 and every bit of `active` set are allowed) when its kernels
+// read the objects through a device table: the source rule S of the object load, whether there is a table and a mask set per
+// variant, and what the host refuses for it.  One row per form; run_entry and move_planes read nothing else, so a new form is a
+// row here, its object load above and its kernels and entries in a unit.
+struct TableForm {
+  Src src;                 // the table's row per (object, frame): table_words
+  bool per_variant;        // [nvar][nobj][frames][..] with masks [nvar][nobj][frames][mask_h][mask_w]
+  const char* null_table;  // the refusal of a null table; nullptr: the entry takes none
+  const char* blend;       // who speaks when a blend entry misses the form's limits
+  const char* mover;       // the form's plane mover, as it names itself in every refusal
+  const char* hw_fits;     // MAP2 / TAPS: the kernels form height * width as an int and (MAP2) a map entry is an int32 -- what a
+                           // site of 2^31 pixels or more does not fit; nullptr: no such limit
+};
+
+constexpr TableForm NO_TABLE = {DIRECT, false, nullptr, nullptr, nullptr, nullptr};
+constexpr TableForm PLACED = {SHIFT, false, "pnp placed: null offset table", nullptr, "shift_planes", nullptr};
+constexpr TableForm PLACED_VARIANTS = {SHIFT, true, "pnp placed: null offset table", nullptr, nullptr, nullptr};
+constexpr TableForm RESAMPLED = {MAP, false, "pnp resampled: null map table", nullptr, "gather_planes", nullptr};
+constexpr TableForm RESAMPLED_VARIANTS = {MAP, true, "pnp resampled variants: null map table", nullptr, nullptr, nullptr};
+constexpr TableForm WARPED = {MAP2, false, "pnp warped: null map table", "pnp warped", "gather_planes_warped", "the int32 map entries"};
+constexpr TableForm BILINEAR = {TAPS, false, "pnp bilinear: null tap table", "pnp bilinear", "gather_planes_bilinear", "an int"};
+
+// int32 words of one table row: [2], [h + w], [h * w] or [h * w][2]
+double table_words(Src s, double h, double w) {
+  switch (s) {
+    case SHIFT: return 2.0;
+    case MAP: return h + w;
+    case MAP2: return h * w;
+    case TAPS: return 2.0 * h * w;
+    default: return 0.0;
+  }
 }
 
-// _placed_variants: the _placed contract with a table and masks per variant.  Traffic in chunks: every injecting variant reads
-// the distinct object chunks at its own pixels (nobjc each) and writes ndst chunks; the base is read once when it is chunk 0,
-// else once per injecting variant
-int fill_placed_variants(const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar, uint32_t active,
-                         const void* place, PnpArgs& a, double& chunks, int& on) {
-  double unused = 0;
-  if (int rc = fill_placed(d, nsrc, obj_chunk, nvar, active, place, a, unused)) return rc;
-  unsigned seen = 0;
-  for (int j = 0; j < d->nobj; ++j) seen |= 1u << obj_chunk[j];
-  on = __builtin_popcount(active);
-  chunks = (double)on * __builtin_popcount(seen) + (d->base_chunk0 ? 1 : on) + (double)a.ndst * on;
+// the table's bytes as the profiler is told them, `rows` = (variants x) objects x frames rows.  The offset table shared by the
+// variants (8 bytes per row) has never been counted, by the _placed entries or by shift_planes
+double table_bytes(const TableForm& t, double rows, int h, int w) {
+  if (t.src == SHIFT && !t.per_variant) return 0.0;
+  return 4.0 * rows * table_words(t.src, h, w);
+}
+
+// the form's limits on a site of h x w; `hname` / `wname`: what the caller's interface calls them.  TAPS: a tap row / column + 1
+// is a 16-bit field of word 0 and 0xffff is kept for "absent": a site with 65 535 rows or columns or more is refused
+int table_limits(const TableForm& t, const char* who, const char* hname, const char* wname, int h, int w) {
+  MVOC_REQUIRE(!t.hw_fits || (long)h * w < 0x7fffffffL, -2, "%s: %s * %s does not fit %s", who, hname, wname, t.hw_fits);
+  MVOC_REQUIRE(t.src != TAPS || (h < 65535 && w < 65535), -2, "%s: %s %d or %s %d does not fit the 16-bit tap fields (< 65535)", who,
+               hname, h, wname, w);
   return 0;
 }
 
@@ -573,6 +607,54 @@ void dispatch(int nobj, bool vec, F&& f) {
 template <class K, class... Args>
 void launch(K kernel, const Launch& l, Args... args) {
   hipLaunchKernelGGL(kernel, l.grid, dim3(256), 0, l.s, args...);
+}
+
+// What every entry that takes variants does, in the order its refusals are promised: no-background, null table, nvar, active, the
+// descriptor, the source map, the form's limits, the layout's preconditions (`prepare` = prepare_tokens / prepare_nchw); then the
+// profiler scope and `launch_inst(NOBJ, VEC, l, a)`, which launches the entry's kernel `kernel` in that instantiation.
+template <class F>
+int run_entry(const char* entry, const char* kernel, const TableForm& t, int (*prepare)(const mvoc_pnp_desc*, PnpArgs&, void*, Launch&),
+              const mvoc_pnp_desc* d, int32_t nsrc, const int32_t* obj_chunk, int32_t nvar, uint32_t active, const void* table,
+              void* stream, F&& launch_inst) {
+  if (int rc = refuse_no_background(d, entry)) return rc;
+  MVOC_REQUIRE(!t.null_table || table, -1, "%s", t.null_table);
+  PnpArgs a;
+  Launch l;
+  double chunks = 0, mask_sets = 1.0;
+  if (int rc = fill_variants_sel(d, nsrc, obj_chunk, nvar, active, a, chunks)) return rc;
+  if (t.per_variant) {
+    // a table and masks per variant.  Traffic in chunks: every injecting variant reads the distinct object chunks at its own
+    // pixels and writes ndst chunks; the base is read once when it is chunk 0, else once per injecting variant
+    unsigned seen = 0;
+    for (int j = 0; j < d->nobj; ++j) seen |= 1u << obj_chunk[j];
+    const int on = __builtin_popcount(active);
+    chunks = (double)on * __builtin_popcount(seen) + (d->base_chunk0 ? 1 : on) + (double)a.ndst * on;
+    mask_sets = on;
+  }
+  if (int rc = table_limits(t, t.blend, "height", "width", d->height, d->width)) return rc;
+  if (int rc = prepare(d, a, stream, l)) return rc;
+  const double rows = (t.per_variant ? (double)nvar : 1.0) * d->nobj * d->frames;
+  MvocProfScope prof(MVOC_FAM_PNP, l.s, blend_bytes(l, d->nobj, chunks, mask_sets, table_bytes(t, rows, d->height, d->width)));
+  dispatch(d->nobj, l.vec, [&](auto n, auto v) { launch_inst(n, v, l, a); });
+  return mvoc_check_launch(kernel);
+}
+
+// What every plane mover does: [nplane][frames][h][w] fp16 planes through one table row per frame, shared by the planes.
+// `launch_k(grid, stream, n)` launches the mover's kernel `kernel` over the n elements.
+template <class F>
+int move_planes(const TableForm& t, const char* kernel, const void* src, void* dst, int32_t nplane, int32_t frames, int32_t h,
+                int32_t w, const void* table, void* stream, F&& launch_k) {
+  MVOC_REQUIRE(src && dst && table, -1, "%s: null operand", t.mover);
+  MVOC_REQUIRE(src != dst, -1, "%s: in place (src == dst) is not supported", t.mover);
+  MVOC_REQUIRE(nplane > 0 && frames > 0 && h > 0 && w > 0, -1, "%s: bad dims", t.mover);
+  if (int rc = table_limits(t, t.mover, "h", "w", h, w)) return rc;
+  const long n = (long)nplane * frames * h * w;
+  const long nblk = (n + 255) / 256;
+  MVOC_REQUIRE(nblk < 0x7fffffffL, -2, "%s: grid too large", t.mover);
+  hipStream_t s = (hipStream_t)stream;
+  MvocProfScope prof(MVOC_FAM_MISC, s, 2.0 * n * 2 + table_bytes(t, frames, h, w));
+  launch_k(dim3((unsigned)nblk), s, n);
+  return mvoc_check_launch(kernel);
 }
 
 }  // namespace

@@ -3,7 +3,9 @@
 PyTorch supplies device memory and the current HIP stream; every computation is a libmvoc_hip kernel.
 All activations are fp16, channels-last 2-D ``[rows, C]`` tensors (rows = B*F*H*W).
 """
+import collections
 import ctypes as C
+import operator
 import os
 import threading
 
@@ -549,85 +551,94 @@ def _active_mask(active, nvar, what):
     return None if active == (1 << nvar) - 1 else active
 
 
+# ---- the table forms: one row per keyword of ``pnp_blend_<layout>`` that hands the blend a device table --------------
+# keyword       the argument of ``pnp_blend_tokens`` / ``pnp_blend_nchw``
+# suffix        the entry is mvoc_pnp_blend_scatter_<layout><suffix>
+# per_variant   a 4-D [K, nobj, F, ..] table next to a [K, nobj, F, mh, mw] mask stack is allowed: <suffix>_variants (6l, 6o)
+# tail          descriptor -> the table's dims after [nobj, F] as (how a message writes it, size)
+# noun          what the message about the mask stack calls a per-variant table, after its shape
+# together      the refusal when a keyword of an EARLIER row is given as well (a later row outranks an earlier one)
+# stack         the refusal of a mask stack that has no per-variant table of this form beside it
+# no_background where ``no_background`` is refused for the keyword: None -- not by name (the positional flag's own refusal in
+#               ``pnp_blend_tokens`` names a placement); "entry" -- where the entry is chosen; "first" -- before that refusal
+_TableForm = collections.namedtuple("_TableForm", "keyword suffix per_variant tail noun together stack no_background")
+_NO_STACK = "does not take a [K, nobj, F, mh, mw] mask stack"
+_TABLE_FORMS = (
+    _TableForm("place", "_placed", True, lambda d: (("2", 2),), "", None,
+               "a [K, nobj, F, mh, mw] mask stack needs place= as an int32 [K, nobj, F, 2] table", None),
+    _TableForm("resample", "_resampled", True, lambda d: (("H + W", d.height + d.width),), " resample",
+               "resample= and place= are both given: a translation is part of the resample table",
+               f"resample= {_NO_STACK}: one transform serves all variants", "entry"),
+    _TableForm("warp", "_warped", False, lambda d: (("H * W", d.height * d.width),), "",
+               "warp= is given together with place= / resample=: the 2-D map carries scale, mirror and translation",
+               f"warp= {_NO_STACK}: one warp serves all variants", "first"),
+    _TableForm("warp_taps", "_bilinear", False, lambda d: (("H * W", d.height * d.width), ("2", 2)), "",
+               "warp_taps= is given together with place= / resample= / warp=: the tap table carries the whole warp",
+               f"warp_taps= {_NO_STACK}: one warp serves all variants", "first"),
+)
+
+
+def _tail_text(tail):
+    return ", ".join(label if label.isdigit() else f"{label} = {size}" for label, size in tail)
+
+
+def _refuse_no_background(what, form):
+    raise RuntimeError(f"{what}: {form.keyword}= with no_background: pass src_map=(nobj, range(nobj)) instead")
+
+
+def _select_entry(what, tables, mask_dim, no_background, src_map, nvar, active):
+    """(suffix, row, table) of the library entry mvoc_pnp_blend_scatter_<layout><suffix> that the arguments of
+    ``pnp_blend_<layout>`` select: by the one table given in ``tables`` (keyword -> table or None; a 3-D table shared by the
+    variants, or where the row allows it a 4-D table per variant, which goes with a 5-D [K, nobj, F, mh, mw] mask stack and the
+    stack with nothing else), else by ``src_map`` / ``nvar`` / ``active``; every other combination is refused"""
+    given = [f for f in _TABLE_FORMS if tables.get(f.keyword) is not None]
+    form = given[-1] if given else None
+    table = tables[form.keyword] if form else None
+    if len(given) > 1:
+        raise RuntimeError(f"{what}: {form.together}")
+    per_variant = form is not None and form.per_variant and torch.is_tensor(table) and table.dim() == 4
+    if mask_dim == 5 and not per_variant:
+        raise RuntimeError(f"{what}: {(form or _TABLE_FORMS[0]).stack}")
+    if form is None:
+        if nvar == 1:
+            return "" if src_map is None else "_mapped", None, None
+        return "_variants" if active is None else "_variants_sel", None, None
+    if no_background and form.no_background:
+        _refuse_no_background(what, form)
+    return form.suffix + ("_variants" if per_variant else ""), form, table
+
+
 def _blend_entry(what, place, resample, mask_dim, no_background, src_map, nvar, active, warp=None, warp_taps=None):
-    """the suffix of the library entry mvoc_pnp_blend_scatter_<layout><suffix> that the arguments of ``pnp_blend_<layout>``
-    select, by the form of ``place`` / ``resample`` (None, a 3-D table shared by the variants, a 4-D table per variant) and of the
-    masks (4-D, or a 5-D [K, nobj, F, mh, mw] stack, which goes with a 4-D table only), or by ``warp`` (a 3-D table shared by the
-    variants) or ``warp_taps`` (a 4-D tap table shared by the variants); every other combination is
-    refused"""
-    dim = lambda t: t.dim() if torch.is_tensor(t) else None
-    if warp_taps is not None:
-        if place is not None or resample is not None or warp is not None:
-            raise RuntimeError(f"{what}: warp_taps= is given together with place= / resample= / warp=: the tap table carries the "
-                               "whole warp")
-        if mask_dim == 5:
-            raise RuntimeError(f"{what}: warp_taps= does not take a [K, nobj, F, mh, mw] mask stack: one warp serves all variants")
-        if no_background:
-            raise RuntimeError(f"{what}: warp_taps= with no_background: pass src_map=(nobj, range(nobj)) instead")
-        return "_bilinear"
-    if warp is not None:
-        if place is not None or resample is not None:
-            raise RuntimeError(f"{what}: warp= is given together with place= / resample=: the 2-D map carries scale, mirror and "
-                               "translation")
-        if mask_dim == 5:
-            raise RuntimeError(f"{what}: warp= does not take a [K, nobj, F, mh, mw] mask stack: one warp serves all variants")
-        if no_background:
-            raise RuntimeError(f"{what}: warp= with no_background: pass src_map=(nobj, range(nobj)) instead")
-        return "_warped"
-    if resample is not None:
-        if place is not None:
-            raise RuntimeError(f"{what}: resample= and place= are both given: a translation is part of the resample table")
-        if mask_dim == 5 and dim(resample) != 4:
-            raise RuntimeError(f"{what}: resample= does not take a [K, nobj, F, mh, mw] mask stack: one transform serves all variants")
-        if no_background:
-            raise RuntimeError(f"{what}: resample= with no_background: pass src_map=(nobj, range(nobj)) instead")
-        return "_resampled_variants" if dim(resample) == 4 else "_resampled"
-    if mask_dim == 5 and dim(place) != 4:
-        raise RuntimeError(f"{what}: a [K, nobj, F, mh, mw] mask stack needs place= as an int32 [K, nobj, F, 2] table")
-    if place is not None:
-        return "_placed_variants" if dim(place) == 4 else "_placed"
-    if nvar == 1:
-        return "" if src_map is None else "_mapped"
-    return "_variants" if active is None else "_variants_sel"
+    """the suffix ``_select_entry`` chooses, with the tables as arguments (``place`` / ``resample``: DESIGN.md 6k-6o, ``warp``: 6q,
+    ``warp_taps``: 6r)"""
+    tables = dict(place=place, resample=resample, warp=warp, warp_taps=warp_taps)
+    return _select_entry(what, tables, mask_dim, no_background, src_map, nvar, active)[0]
 
 
 def _check_table(what, name, table, masks, nvar, d):
-    """the form of a ``place`` ([.., 2]), ``resample`` ([.., H + W]), ``warp`` ([nobj, F, H * W], never per variant) or
-    ``warp_taps`` ([nobj, F, H * W, 2], never per variant) table
-    against the descriptor: int32 [nobj, F, ..], or per variant [K, nobj, F, ..] next to a [K, nobj, F, mh, mw]
-    mask stack"""
+    """the form of the table of keyword ``name`` against the descriptor: int32 [nobj, F, <the row's tail>], or where the row allows
+    it per variant [K, nobj, F, ..] next to a [K, nobj, F, mh, mw] mask stack"""
     _chk(table, name, torch.int32)
-    if name == "warp_taps":
-        shape = (d.nobj, d.frames, d.height * d.width, 2)
-        if tuple(table.shape) != shape or not table.is_contiguous():
-            raise RuntimeError(f"{what}: warp_taps must be a contiguous int32 [nobj = {d.nobj}, F = {d.frames}, H * W = {shape[2]}, 2] "
-                               f"table, got {tuple(table.shape)}")
-        return
-    if name == "warp":
-        shape = (d.nobj, d.frames, d.height * d.width)
-        if tuple(table.shape) != shape or not table.is_contiguous():
-            raise RuntimeError(f"{what}: warp must be a contiguous int32 [nobj = {d.nobj}, F = {d.frames}, H * W = {shape[2]}] "
-                               f"table, got {tuple(table.shape)}")
-        return
-    last, size = ("2", 2) if name == "place" else ("H + W", d.height + d.width)
-    shape, dims = (d.nobj, d.frames, size), f"nobj = {d.nobj}, F = {d.frames}"
-    if table.dim() == 4:
+    form = next(f for f in _TABLE_FORMS if f.keyword == name)
+    tail = form.tail(d)
+    shape, dims = (d.nobj, d.frames) + tuple(size for _, size in tail), f"nobj = {d.nobj}, F = {d.frames}"
+    per_variant = form.per_variant and table.dim() == 4
+    if per_variant:
         shape, dims = (int(nvar),) + shape, f"K = {int(nvar)}, " + dims
     if tuple(table.shape) != shape or not table.is_contiguous():
-        raise RuntimeError(f"{what}: {name} must be a contiguous int32 [{dims}, {last if name == 'place' else f'H + W = {size}'}] table"
-                           f"{' with a [K, nobj, F, mh, mw] mask stack' if table.dim() == 4 else ''}, got {tuple(table.shape)}")
-    if table.dim() == 4 and (masks.dim() != 5 or tuple(masks.shape[:3]) != shape[:3] or not masks.is_contiguous()):
-        raise RuntimeError(f"{what}: a [K, nobj, F, {last}]{' resample' if name == 'resample' else ''} table needs masks as a "
+        raise RuntimeError(f"{what}: {name} must be a contiguous int32 [{dims}, {_tail_text(tail)}] table"
+                           f"{' with a [K, nobj, F, mh, mw] mask stack' if per_variant else ''}, got {tuple(table.shape)}")
+    if per_variant and (masks.dim() != 5 or tuple(masks.shape[:3]) != shape[:3] or not masks.is_contiguous()):
+        raise RuntimeError(f"{what}: a [K, nobj, F, {', '.join(label for label, _ in tail)}]{form.noun} table needs masks as a "
                            f"contiguous [{dims}, mh, mw] stack, got {tuple(masks.shape)}")
 
 
-def _pnp_blend(layout, d, x, x2, masks, need, ndst, src_map, nvar, active, place, resample, no_background=False, warp=None,
-               warp_taps=None):
+def _pnp_blend(layout, d, x, x2, masks, need, ndst, src_map, nvar, active, tables, no_background=False):
     """call the library entry mvoc_pnp_blend_scatter_<layout><suffix> that the arguments of ``pnp_blend_<layout>`` select
-    (``_blend_entry``) on the descriptor ``d``; ``need(nchunk)``: elements a tensor must hold from its first for a batch of
+    (``_select_entry``) on the descriptor ``d``; ``need(nchunk)``: elements a tensor must hold from its first for a batch of
     nchunk chunks"""
     what = f"pnp_blend_{layout}"
-    suffix = _blend_entry(what, place, resample, masks.dim(), no_background, src_map, nvar, active, warp, warp_taps)
+    suffix, form, table = _select_entry(what, tables, masks.dim(), no_background, src_map, nvar, active)
 
     def call(*args):
         name = f"pnp_blend_scatter_{layout}{suffix}"
@@ -643,10 +654,8 @@ def _pnp_blend(layout, d, x, x2, masks, need, ndst, src_map, nvar, active, place
         return call(nsrc, chunks, int(nvar))
     if suffix == "_variants_sel":
         return call(nsrc, chunks, int(nvar), active)
-    # a table: the _placed / _resampled / _warped / _bilinear entries take the bitmask in every case (all bits: every variant injects)
-    name, table = (("warp_taps", warp_taps) if warp_taps is not None else ("warp", warp) if warp is not None else
-                   ("place", place) if place is not None else ("resample", resample))
-    _check_table(what, name, table, masks, nvar, d)
+    # a table: its entries take the bitmask in every case (all bits: every variant injects)
+    _check_table(what, form.keyword, table, masks, nvar, d)
     return call(nsrc, chunks, int(nvar), _all_or(active, nvar), table.data_ptr())
 
 
@@ -677,13 +686,13 @@ def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride,
     ``src_map`` / ``active`` are.  Not with ``place`` / ``resample`` / ``warp``, a per-variant mask stack or ``no_background``."""
     d = _pnp_desc(x, x2, masks, chunk_stride, f_stride, p_stride, frames, height, width, channels, base_chunk0, ndst)
     active = _active_mask(active, nvar, "pnp_blend_tokens")
+    tables = dict(place=place, resample=resample, warp=warp, warp_taps=warp_taps)
     if no_background:
         if base_chunk0:
             raise RuntimeError("pnp_blend_tokens: no_background with base_chunk0: the base would be the chunk the batch does not hold")
-        if warp is not None:
-            raise RuntimeError("pnp_blend_tokens: warp= with no_background: pass src_map=(nobj, range(nobj)) instead")
-        if warp_taps is not None:
-            raise RuntimeError("pnp_blend_tokens: warp_taps= with no_background: pass src_map=(nobj, range(nobj)) instead")
+        for form in _TABLE_FORMS:
+            if form.no_background == "first" and tables[form.keyword] is not None:
+                _refuse_no_background("pnp_blend_tokens", form)
         if src_map is not None or nvar != 1 or place is not None or active is not None:
             raise RuntimeError("pnp_blend_tokens: no_background is the positional entry's flag; with a source map, variants or a "
                                "placement pass src_map=(nobj, range(nobj)) instead")
@@ -691,8 +700,8 @@ def pnp_blend_tokens(x, masks, *, frames, height, width, channels, chunk_stride,
         _check_variants(x, x2, 1, last + (frames - 1) * f_stride + (height * width - 1) * p_stride + channels, "pnp_blend_tokens")
         d.base_chunk0 = -1  # (include/mvoc_hip.h: no background chunk, the base is the last chunk)
     reach = (frames - 1) * f_stride + (height * width - 1) * p_stride + channels  # of the last chunk's last element
-    _pnp_blend("tokens", d, x, x2, masks, lambda nchunk: (nchunk - 1) * chunk_stride + reach, ndst, src_map, nvar, active, place,
-               resample, no_background, warp, warp_taps)
+    _pnp_blend("tokens", d, x, x2, masks, lambda nchunk: (nchunk - 1) * chunk_stride + reach, ndst, src_map, nvar, active, tables,
+               no_background)
     return x
 
 
@@ -706,8 +715,8 @@ def pnp_blend_nchw(x, masks, *, frames, x2=None, base_chunk0=True, ndst=2, src_m
         raise RuntimeError("pnp_blend_nchw: x must be contiguous [N, C, H, W]")
     d = _pnp_desc(x, x2, masks, 0, 0, 0, frames, x.shape[2], x.shape[3], x.shape[1], base_chunk0, ndst)
     active = _active_mask(active, nvar, "pnp_blend_nchw")
-    _pnp_blend("nchw", d, x, x2, masks, lambda nchunk: nchunk * frames * x[0].numel(), ndst, src_map, nvar, active, place, resample,
-               warp=warp, warp_taps=warp_taps)
+    _pnp_blend("nchw", d, x, x2, masks, lambda nchunk: nchunk * frames * x[0].numel(), ndst, src_map, nvar, active,
+               dict(place=place, resample=resample, warp=warp, warp_taps=warp_taps))
     return x
 
 
@@ -738,17 +747,23 @@ def place_table(placement, height, width, mask_h, mask_w, device):
     return torch.tensor(lv, dtype=torch.int32).to(device).contiguous()
 
 
+def _per_variant(what, variants, noun, table):
+    """[``table(v)`` for v in variants]; a refusal names the variant it came from"""
+    if not variants:
+        raise RuntimeError(f"{what}: needs at least one variant's {noun}")
+    out = []
+    for k, v in enumerate(variants):
+        try:
+            out.append(table(v))
+        except RuntimeError as e:
+            raise RuntimeError(f"{what}: variant {k}: {e}") from None
+    return out
+
+
 def place_table_variants(placements, height, width, mask_h, mask_w, device):
     """the device table the ``_placed_variants`` blend entries read: int32 [K, nobj, F, 2], row k = ``place_table`` of
     ``placements[k]`` (the same rule, ``level_offset``, and the same int32 refusal)"""
-    if not placements:
-        raise RuntimeError("place_table_variants: needs at least one variant's placement")
-    tabs = []
-    for k, pl in enumerate(placements):
-        try:
-            tabs.append(place_table(pl, height, width, mask_h, mask_w, "cpu"))
-        except RuntimeError as e:
-            raise RuntimeError(f"place_table_variants: variant {k}: {e}") from None
+    tabs = _per_variant("place_table_variants", placements, "placement", lambda pl: place_table(pl, height, width, mask_h, mask_w, "cpu"))
     if len({tuple(t.shape) for t in tabs}) != 1:
         raise RuntimeError(f"place_table_variants: the variants' tables differ in shape: {[tuple(t.shape) for t in tabs]}")
     return torch.stack(tabs).to(device).contiguous()
@@ -759,23 +774,31 @@ def _all_or(active, nvar):
     return (1 << int(nvar)) - 1 if active is None else active
 
 
-def shift_planes(src, offsets, out=None):
-    """zero-filled per-frame integer translation of contiguous fp16 planes [..., F, h, w] (leading dims = planes of ONE
-    object): out[.., f, y, x] = src[.., f, y - dy_f, x - dx_f] or 0.  ``offsets``: device int32 [F, 2] = (dy_f, dx_f)."""
-    _chk(src, "src"), _chk(offsets, "offsets", torch.int32)
+def _move_planes(what, entry, src, table, tail, out, name):
+    """what the four plane movers share: contiguous fp16 planes ``src`` [..., F, h, w] through the device table ``table`` (the
+    argument ``name`` of ``what``), int32 [F, <tail(h, w)>] with the dims as (how a message writes it, size), into ``out`` (None: a new
+    tensor) by the library's mvoc_<entry>_f16"""
+    _chk(src, "src"), _chk(table, name, torch.int32)
     if src.dim() < 3 or not src.is_contiguous():
-        raise RuntimeError(f"shift_planes: src must be contiguous [..., F, h, w], got {tuple(src.shape)}")
+        raise RuntimeError(f"{what}: src must be contiguous [..., F, h, w], got {tuple(src.shape)}")
     frames, h, w = src.shape[-3:]
-    if tuple(offsets.shape) != (frames, 2) or not offsets.is_contiguous():
-        raise RuntimeError(f"shift_planes: offsets must be a contiguous int32 [F = {frames}, 2] table, got {tuple(offsets.shape)}")
+    dims = tail(h, w)
+    if tuple(table.shape) != (frames,) + tuple(size for _, size in dims) or not table.is_contiguous():
+        raise RuntimeError(f"{what}: {name} must be a contiguous int32 [F = {frames}, {_tail_text(dims)}] table, got {tuple(table.shape)}")
     if out is None:
         out = torch.empty_like(src)
     _chk(out, "out")
     if out.shape != src.shape or not out.is_contiguous():
-        raise RuntimeError("shift_planes: out must be contiguous and of src's shape")
-    check(lib.mvoc_shift_planes_f16(src.data_ptr(), out.data_ptr(), src.numel() // (frames * h * w), frames, h, w, offsets.data_ptr(),
-                                    _stream()), "shift_planes")
+        raise RuntimeError(f"{what}: out must be contiguous and of src's shape")
+    check(getattr(lib, f"mvoc_{entry}_f16")(src.data_ptr(), out.data_ptr(), src.numel() // (frames * h * w), frames, h, w,
+                                            table.data_ptr(), _stream()), entry)
     return out
+
+
+def shift_planes(src, offsets, out=None):
+    """zero-filled per-frame integer translation of contiguous fp16 planes [..., F, h, w] (leading dims = planes of ONE
+    object): out[.., f, y, x] = src[.., f, y - dy_f, x - dx_f] or 0.  ``offsets``: device int32 [F, 2] = (dy_f, dx_f)."""
+    return _move_planes("shift_planes", "shift_planes", src, offsets, lambda h, w: (("2", 2),), out, name="offsets")
 
 
 # ---- scale and mirror: nearest resampling through per-axis index maps (DESIGN.md 6n) ---------------------------------------
@@ -826,14 +849,8 @@ def resample_table(transform, height, width, mask_h, mask_w, device):
 def resample_table_variants(variant_transforms, height, width, mask_h, mask_w, device):
     """the device table the ``_resampled_variants`` blend entries read: int32 [K, nobj, F, height + width], row k
     = ``resample_table`` of ``variant_transforms[k]`` (the same rule, ``level_axis_map``)"""
-    if not variant_transforms:
-        raise RuntimeError("resample_table_variants: needs at least one variant's transform")
-    rows = []
-    for k, tr in enumerate(variant_transforms):
-        try:
-            rows.append(transform_maps(tr, height, width, mask_h, mask_w))
-        except RuntimeError as e:
-            raise RuntimeError(f"resample_table_variants: variant {k}: {e}") from None
+    rows = _per_variant("resample_table_variants", variant_transforms, "transform",
+                        lambda tr: transform_maps(tr, height, width, mask_h, mask_w))
     shapes = {(len(r), len(r[0])) for r in rows}
     if len(shapes) != 1:
         raise RuntimeError(f"resample_table_variants: the variants' tables differ in shape (objects, frames): {sorted(shapes)}")
@@ -843,20 +860,7 @@ def resample_table_variants(variant_transforms, height, width, mask_h, mask_w, d
 def gather_planes(src, maps, out=None):
     """zero-filled per-frame gather of contiguous fp16 planes [..., F, h, w] (leading dims = planes of ONE object):
     out[.., f, y, x] = src[.., f, ymap_f[y], xmap_f[x]] or 0 where either index is outside.  ``maps``: device int32 [F, h + w]."""
-    _chk(src, "src"), _chk(maps, "maps", torch.int32)
-    if src.dim() < 3 or not src.is_contiguous():
-        raise RuntimeError(f"gather_planes: src must be contiguous [..., F, h, w], got {tuple(src.shape)}")
-    frames, h, w = src.shape[-3:]
-    if tuple(maps.shape) != (frames, h + w) or not maps.is_contiguous():
-        raise RuntimeError(f"gather_planes: maps must be a contiguous int32 [F = {frames}, h + w = {h + w}] table, got {tuple(maps.shape)}")
-    if out is None:
-        out = torch.empty_like(src)
-    _chk(out, "out")
-    if out.shape != src.shape or not out.is_contiguous():
-        raise RuntimeError("gather_planes: out must be contiguous and of src's shape")
-    check(lib.mvoc_gather_planes_f16(src.data_ptr(), out.data_ptr(), src.numel() // (frames * h * w), frames, h, w, maps.data_ptr(),
-                                     _stream()), "gather_planes")
-    return out
+    return _move_planes("gather_planes", "gather_planes", src, maps, lambda h, w: (("h + w", h + w),), out, name="maps")
 
 
 # ---- rotation: nearest resampling through ONE 2-D index map (DESIGN.md 6q) --------------------------------------------------
@@ -879,29 +883,42 @@ def warp_numerator_bound(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw):
     return max(numy, numx, 2 * den * W * Lh, 2 * den * H * Lw, H * W)
 
 
-def _level_warp_map_py(dy, dx, myy, myx, mxy, mxx, den, ay2, ax2, H, W, Lh, Lw):
+def _warp_coords_py(dy, dx, myy, myx, mxy, mxx, den, ay2, ax2, H, W, Lh, Lw):
+    """the source coordinate of every destination pixel, row by row, as one exact rational per axis: (Ny, Dy, Nx, Dx), the
+    coordinate Ny / Dy rows and Nx / Dx columns.  Python ints: the definition.  ``level_warp_map`` floors them, ``level_warp_taps``
+    splits them into a tap and a weight"""
     dfy, dfx = level_offset(dy, H, Lh), level_offset(dx, W, Lw)
-    cy, cx, qy, qx = ay2 * den * H * W, ax2 * den * H * W, 2 * den * W * Lh, 2 * den * H * Lw
-    out = []
+    cy, cx, Dy, Dx = ay2 * den * H * W, ax2 * den * H * W, 2 * den * W * Lh, 2 * den * H * Lw
     for iy in range(H):
         ny = (2 * (iy - dfy) + 1) * Lh - ay2 * H
         for ix in range(W):
             nx = (2 * (ix - dfx) + 1) * Lw - ax2 * W
-            sy = (cy + myy * ny * W + myx * nx * H) // qy
-            sx = (cx + mxy * ny * W + mxx * nx * H) // qx
-            out.append(sy * W + sx if 0 <= sy < H and 0 <= sx < W else -1)
-    return out
+            yield cy + myy * ny * W + myx * nx * H, Dy, cx + mxy * ny * W + mxx * nx * H, Dx
 
 
-def _level_warp_map_i64(dy, dx, myy, myx, mxy, mxx, den, ay2, ax2, H, W, Lh, Lw):
-    """``_level_warp_map_py`` on int64 tensors (floor division of integers: exact) -- only below ``warp_numerator_bound`` 2^62"""
+def _warp_coords_i64(dy, dx, myy, myx, mxy, mxx, den, ay2, ax2, H, W, Lh, Lw):
+    """``_warp_coords_py`` on int64 tensors: (Ny [H, W], Dy, Nx [H, W], Dx) -- exact only below the bound its caller checks"""
     dfy, dfx = level_offset(dy, H, Lh), level_offset(dx, W, Lw)
     ny = ((2 * (torch.arange(H, dtype=torch.int64) - dfy) + 1) * Lh - ay2 * H)[:, None]
     nx = ((2 * (torch.arange(W, dtype=torch.int64) - dfx) + 1) * Lw - ax2 * W)[None, :]
-    sy = torch.div(ay2 * den * H * W + myy * W * ny + myx * H * nx, 2 * den * W * Lh, rounding_mode="floor")
-    sx = torch.div(ax2 * den * H * W + mxy * W * ny + mxx * H * nx, 2 * den * H * Lw, rounding_mode="floor")
-    inside = (sy >= 0) & (sy < H) & (sx >= 0) & (sx < W)
-    return torch.where(inside, sy * W + sx, torch.full_like(sy, -1)).reshape(-1).tolist()
+    return (ay2 * den * H * W + myy * W * ny + myx * H * nx, 2 * den * W * Lh,
+            ax2 * den * H * W + mxy * W * ny + mxx * H * nx, 2 * den * H * Lw)
+
+
+def _fdiv(a, b):
+    return torch.div(a, b, rounding_mode="floor")  # floor division of integers: exact
+
+
+def _warp_coords(what, bound, form, term, args):
+    """the coordinates of ``_warp_args`` ``args`` in the form that ``form`` (None, "py", "i64") and ``bound`` select: the int64
+    tensors only while ``bound`` stays below 2^62, else (or when forced) the generator of Python ints -> (is_i64, coordinates)"""
+    fits = bound < 2 ** 62
+    if form == "i64" and not fits:
+        raise RuntimeError(f"{what}: the int64 form is not exact for these arguments ({term} may reach 2^62)")
+    if form not in (None, "py", "i64"):
+        raise RuntimeError(f"{what}: form {form!r} is not one of None, 'py', 'i64'")
+    i64 = fits and form != "py"
+    return i64, (_warp_coords_i64 if i64 else _warp_coords_py)(*args)
 
 
 def level_warp_map(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw, form=None):
@@ -913,19 +930,28 @@ def level_warp_map(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw, form=None):
     only while ``warp_numerator_bound`` stays below 2^62 (``form`` = "py" / "i64" forces one: tests).  A diagonal matrix is the
     outer combination of ``level_axis_map`` of the two axes."""
     args = _warp_args(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw)
-    fits = warp_numerator_bound(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw) < 2 ** 62
-    if form == "i64" and not fits:
-        raise RuntimeError("level_warp_map: the int64 form is not exact for these arguments (a numerator may reach 2^62)")
-    if form not in (None, "py", "i64"):
-        raise RuntimeError(f"level_warp_map: form {form!r} is not one of None, 'py', 'i64'")
-    return _level_warp_map_i64(*args) if fits and form != "py" else _level_warp_map_py(*args)
+    H, W = args[9], args[10]
+    i64, coords = _warp_coords("level_warp_map", warp_numerator_bound(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw), form, "a numerator", args)
+    if i64:
+        Ny, Dy, Nx, Dx = coords
+        sy, sx = _fdiv(Ny, Dy), _fdiv(Nx, Dx)
+        inside = (sy >= 0) & (sy < H) & (sx >= 0) & (sx < W)
+        return torch.where(inside, sy * W + sx, torch.full_like(sy, -1)).reshape(-1).tolist()
+    out = []
+    for Ny, Dy, Nx, Dx in coords:
+        sy, sx = Ny // Dy, Nx // Dx
+        out.append(sy * W + sx if 0 <= sy < H and 0 <= sx < W else -1)
+    return out
 
 
-def warp_maps(warp, height, width, mask_h, mask_w):
-    """``warp`` = per object (ay2, ax2, ((myy, myx, mxy, mxx, den, dy, dx) per frame)) -> nested lists [nobj][F][height * width]:
-    per frame ``level_warp_map``, computed once per distinct frame value of an object"""
+def _check_frames(what, warp):
     if not warp or len({len(w[2]) for w in warp}) != 1 or not warp[0][2]:
-        raise RuntimeError("warp_maps: every object needs the same number (>= 1) of per-frame matrices")
+        raise RuntimeError(f"{what}: every object needs the same number (>= 1) of per-frame matrices")
+
+
+def _per_frame(warp, level):
+    """``warp`` = per object (ay2, ax2, ((myy, myx, mxy, mxx, den, dy, dx) per frame)) -> nested lists [nobj][F] of
+    ``level(dy, dx, (myy, myx, mxy, mxx), den, ay2, ax2)``, computed once per distinct frame value of an object"""
     rows = []
     for ay2, ax2, frames in warp:
         cache = {}
@@ -934,10 +960,17 @@ def warp_maps(warp, height, width, mask_h, mask_w):
             fr = tuple(fr)
             if fr not in cache:
                 myy, myx, mxy, mxx, den, dy, dx = fr
-                cache[fr] = level_warp_map(dy, dx, (myy, myx, mxy, mxx), den, ay2, ax2, height, width, mask_h, mask_w)
+                cache[fr] = level(dy, dx, (myy, myx, mxy, mxx), den, ay2, ax2)
             obj.append(cache[fr])
         rows.append(obj)
     return rows
+
+
+def warp_maps(warp, height, width, mask_h, mask_w):
+    """``warp`` = per object (ay2, ax2, ((myy, myx, mxy, mxx, den, dy, dx) per frame)) -> nested lists [nobj][F][height * width]:
+    per frame ``level_warp_map``, computed once per distinct frame value of an object"""
+    _check_frames("warp_maps", warp)
+    return _per_frame(warp, lambda *a: level_warp_map(*a, height, width, mask_h, mask_w))
 
 
 def warp_table(warp, height, width, mask_h, mask_w, device):
@@ -951,20 +984,7 @@ def warp_table(warp, height, width, mask_h, mask_w, device):
 def warp_planes(src, map, out=None):
     """zero-filled per-frame gather of contiguous fp16 planes [..., F, h, w] (leading dims = planes of ONE object) through a 2-D
     map: out[.., f, pix] = src[.., f, map_f[pix]] or 0 where the entry is outside.  ``map``: device int32 [F, h * w]."""
-    _chk(src, "src"), _chk(map, "map", torch.int32)
-    if src.dim() < 3 or not src.is_contiguous():
-        raise RuntimeError(f"warp_planes: src must be contiguous [..., F, h, w], got {tuple(src.shape)}")
-    frames, h, w = src.shape[-3:]
-    if tuple(map.shape) != (frames, h * w) or not map.is_contiguous():
-        raise RuntimeError(f"warp_planes: map must be a contiguous int32 [F = {frames}, h * w = {h * w}] table, got {tuple(map.shape)}")
-    if out is None:
-        out = torch.empty_like(src)
-    _chk(out, "out")
-    if out.shape != src.shape or not out.is_contiguous():
-        raise RuntimeError("warp_planes: out must be contiguous and of src's shape")
-    check(lib.mvoc_gather_planes_warped_f16(src.data_ptr(), out.data_ptr(), src.numel() // (frames * h * w), frames, h, w,
-                                            map.data_ptr(), _stream()), "gather_planes_warped")
-    return out
+    return _move_planes("warp_planes", "gather_planes_warped", src, map, lambda h, w: (("h * w", h * w),), out, name="map")
 
 
 # ---- bilinear sampling of warped objects: four taps and fixed-point weights per pixel (DESIGN.md 6r) ------------------------------
@@ -979,52 +999,26 @@ def warp_taps_bound(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw):
     return 513 * warp_numerator_bound(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw)
 
 
-def _axis_tap(N, D):
-    T = 2 * N - D                   # the source coordinate minus half a pixel, over 2D
-    i0 = T // (2 * D)               # floor: the upper / left tap
-    q = (TAP_WEIGHT_ONE * (T - i0 * 2 * D) + D) // (2 * D)  # round half up: the weight of tap i0 + 1, 0..256
+def _axis_tap(N, D, fdiv=operator.floordiv):
+    T = 2 * N - D                       # the source coordinate minus half a pixel, over 2D
+    i0 = fdiv(T, 2 * D)                 # floor: the upper / left tap
+    q = fdiv(TAP_WEIGHT_ONE * (T - i0 * 2 * D) + D, 2 * D)  # round half up: the weight of tap i0 + 1, 0..256
     return i0, q
 
 
-def _level_warp_taps_py(dy, dx, myy, myx, mxy, mxx, den, ay2, ax2, H, W, Lh, Lw):
-    dfy, dfx = level_offset(dy, H, Lh), level_offset(dx, W, Lw)
-    cy, cx, Dy, Dx = ay2 * den * H * W, ax2 * den * H * W, 2 * den * W * Lh, 2 * den * H * Lw
-    out = []
-    for iy in range(H):
-        ny = (2 * (iy - dfy) + 1) * Lh - ay2 * H
-        for ix in range(W):
-            nx = (2 * (ix - dfx) + 1) * Lw - ax2 * W
-            y0, qy = _axis_tap(cy + myy * ny * W + myx * nx * H, Dy)
-            x0, qx = _axis_tap(cx + mxy * ny * W + mxx * nx * H, Dx)
-            out.append((y0, x0, qy, qx))
-    return out
-
-
-def _level_warp_taps_i64(dy, dx, myy, myx, mxy, mxx, den, ay2, ax2, H, W, Lh, Lw):
-    """``_level_warp_taps_py`` on int64 tensors (floor division of integers: exact) -- only below ``warp_taps_bound`` 2^62;
-    returns an int64 tensor [H * W, 4]"""
-    dfy, dfx = level_offset(dy, H, Lh), level_offset(dx, W, Lw)
-    ny = ((2 * (torch.arange(H, dtype=torch.int64) - dfy) + 1) * Lh - ay2 * H)[:, None]
-    nx = ((2 * (torch.arange(W, dtype=torch.int64) - dfx) + 1) * Lw - ax2 * W)[None, :]
-    fdiv = lambda a, b: torch.div(a, b, rounding_mode="floor")
-    cols = []
-    for N, D in ((ay2 * den * H * W + myy * W * ny + myx * H * nx, 2 * den * W * Lh),
-                 (ax2 * den * H * W + mxy * W * ny + mxx * H * nx, 2 * den * H * Lw)):
-        T = 2 * N - D
-        i0 = fdiv(T, 2 * D)
-        cols.append((i0, fdiv(TAP_WEIGHT_ONE * (T - i0 * (2 * D)) + D, 2 * D)))
-    (y0, qy), (x0, qx) = cols
-    return torch.stack([y0, x0, qy, qx], dim=-1).reshape(H * W, 4)
-
-
 def _level_warp_taps(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw, form):
+    """``level_warp_taps`` as a list of tuples (the Python ints) or an int64 tensor [H * W, 4] (the int64 form)"""
     args = _warp_args(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw)
-    fits = warp_taps_bound(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw) < 2 ** 62
-    if form == "i64" and not fits:
-        raise RuntimeError("level_warp_taps: the int64 form is not exact for these arguments (a term may reach 2^62)")
-    if form not in (None, "py", "i64"):
-        raise RuntimeError(f"level_warp_taps: form {form!r} is not one of None, 'py', 'i64'")
-    return _level_warp_taps_i64(*args) if fits and form != "py" else _level_warp_taps_py(*args)
+    i64, coords = _warp_coords("level_warp_taps", warp_taps_bound(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw), form, "a term", args)
+    if i64:
+        Ny, Dy, Nx, Dx = coords
+        (y0, qy), (x0, qx) = _axis_tap(Ny, Dy, _fdiv), _axis_tap(Nx, Dx, _fdiv)
+        return torch.stack([y0, x0, qy, qx], dim=-1).reshape(args[9] * args[10], 4)
+    out = []
+    for Ny, Dy, Nx, Dx in coords:
+        (y0, qy), (x0, qx) = _axis_tap(Ny, Dy), _axis_tap(Nx, Dx)
+        out.append((y0, x0, qy, qx))
+    return out
 
 
 def level_warp_taps(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw, form=None):
@@ -1074,23 +1068,12 @@ def _level_tap_words(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw):
 def warp_taps(warp, height, width, mask_h, mask_w):
     """``warp`` (the value of ``warp_maps``) -> an int32 tensor [nobj, F, height * width, 2] on the CPU: per frame the packed
     ``level_warp_taps``, computed once per distinct frame value of an object"""
-    if not warp or len({len(w[2]) for w in warp}) != 1 or not warp[0][2]:
-        raise RuntimeError("warp_taps: every object needs the same number (>= 1) of per-frame matrices")
+    _check_frames("warp_taps", warp)
     if height >= TAP_SITE_LIMIT or width >= TAP_SITE_LIMIT:
         raise RuntimeError(f"warp_taps: {height} x {width}: a site of {TAP_SITE_LIMIT} rows or columns or more does not fit the "
                            "16-bit tap fields")
-    rows = []
-    for ay2, ax2, frames in warp:
-        cache = {}
-        obj = []
-        for fr in frames:
-            fr = tuple(fr)
-            if fr not in cache:
-                myy, myx, mxy, mxx, den, dy, dx = fr
-                cache[fr] = _level_tap_words(dy, dx, (myy, myx, mxy, mxx), den, ay2, ax2, height, width, mask_h, mask_w)
-            obj.append(cache[fr])
-        rows.append(torch.stack(obj))
-    return torch.stack(rows).contiguous()
+    rows = _per_frame(warp, lambda *a: _level_tap_words(*a, height, width, mask_h, mask_w))
+    return torch.stack([torch.stack(obj) for obj in rows]).contiguous()
 
 
 def warp_tap_table(warp, height, width, mask_h, mask_w, device):
@@ -1103,21 +1086,8 @@ def warp_planes_bilinear(src, taps, out=None):
     """zero-filled per-frame bilinear gather of contiguous fp16 planes [..., F, h, w] (leading dims = planes of ONE object)
     through a tap table: out[.., f, pix] = the fp16 chain of DESIGN.md 6r on the four taps of taps_f[pix], 0 where none lies
     inside.  ``taps``: device int32 [F, h * w, 2]."""
-    _chk(src, "src"), _chk(taps, "taps", torch.int32)
-    if src.dim() < 3 or not src.is_contiguous():
-        raise RuntimeError(f"warp_planes_bilinear: src must be contiguous [..., F, h, w], got {tuple(src.shape)}")
-    frames, h, w = src.shape[-3:]
-    if tuple(taps.shape) != (frames, h * w, 2) or not taps.is_contiguous():
-        raise RuntimeError(f"warp_planes_bilinear: taps must be a contiguous int32 [F = {frames}, h * w = {h * w}, 2] table, got "
-                           f"{tuple(taps.shape)}")
-    if out is None:
-        out = torch.empty_like(src)
-    _chk(out, "out")
-    if out.shape != src.shape or not out.is_contiguous():
-        raise RuntimeError("warp_planes_bilinear: out must be contiguous and of src's shape")
-    check(lib.mvoc_gather_planes_bilinear_f16(src.data_ptr(), out.data_ptr(), src.numel() // (frames * h * w), frames, h, w,
-                                              taps.data_ptr(), _stream()), "gather_planes_bilinear")
-    return out
+    return _move_planes("warp_planes_bilinear", "gather_planes_bilinear", src, taps, lambda h, w: (("h * w", h * w), ("2", 2)), out,
+                        name="taps")
 
 
 def ddim_step(x, v_cond, coef_dev, v_uncond=None, out=None):
