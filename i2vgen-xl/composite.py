@@ -17,6 +17,9 @@ An entry's ``obj_transform: [{offset, scale, flip, anchor, rotate}, ...]`` (one 
 mirrors, turns (``rotate``: degrees counter-clockwise or one angle per frame, not in a variant's ``transform``) and places the objects at composition time (``transform_kwargs``; shared by the entry's variants, not with ``obj_offset`` or a
 variant's ``placement``).  A variant's ``transform: [{...}, ...]`` (the format of ``obj_transform``) transforms the objects for
 that variant alone; a variant without the key takes the entry's ``obj_transform``, or none.
+An entry's ``compose_main: true`` has the call build the main conditioning frames from the background and object
+frames under the entry's own placement (``compose_main_kwargs``): ``edited_first_frame_path`` and
+``edited_contorl_frame_path_main`` are not loaded, and the composed frames are written as ``main_00000.png`` ... beside each output.
 """
 import argparse
 import json
@@ -213,6 +216,30 @@ def transform_kwargs(config, variants=None):
     return {"obj_transforms": plain(config.obj_transform), **_filter_kwargs(config)}
 
 
+def compose_main_kwargs(config, variants=None):
+    """the entry's optional ``compose_main: true`` -> keyword arguments of the sampling call: none without the key
+    (exactly today's call), else ``compose_main_images=True`` -- the call builds the main conditioning frames from the background
+    and object frames under the entry's own placement, and ``edited_first_frame_path`` / ``edited_contorl_frame_path_main`` are
+    not loaded (they may be empty).  A variant that overrides either of the two next to the key is an error: there is nothing
+    of the variant's to show, its frames are composed under its own ``placement`` / ``transform``."""
+    if "compose_main" not in config or not config.compose_main:
+        return {}
+    if config.compose_main is not True:
+        raise ValueError(f"compose_main {config.compose_main!r} is not true or false")
+    for k, c in enumerate(variants or ()):
+        for key in ("edited_first_frame_path", "edited_contorl_frame_path_main"):
+            if getattr(c, key) != getattr(config, key):
+                raise ValueError(f"variants[{k}] overrides '{key}' and the entry sets compose_main: the main frames are composed "
+                                 "from the sources, under the variant's own placement or transform")
+    return {"compose_main_images": True}
+
+
+def _write_main_frames(frames, output_dir):
+    """what the model was conditioned on, beside the output: ``main_00000.png`` ..."""
+    for i, f in enumerate(frames):
+        f.save(os.path.join(output_dir, f"main_{i:05d}.png"))
+
+
 def variant_output_dir(config, k):
     """``<output_dir>/<output_suffix of the variant's merged config>/variant_{k:02d}``"""
     return os.path.join(config.output_dir, output_suffix(config), f"variant_{k:02d}")
@@ -238,8 +265,9 @@ def main(template_config, configs_list, device, synthetic=False, dedup_sources=F
         logger.info(f"config: {OmegaConf.to_yaml(config)}")
         size = tuple(config.image_size)
         first = lambda c: load_image(c.edited_first_frame_path).resize(size, resample=Image.Resampling.LANCZOS)
-        main_1st = first(config)
-        main_frames = _frames(config.edited_contorl_frame_path_main, config.n_frames, config.image_size)
+        compose = compose_main_kwargs(config, variants)  # compose_main: the call builds the main frames, none is loaded
+        main_1st = None if compose else first(config)
+        main_frames = None if compose else _frames(config.edited_contorl_frame_path_main, config.n_frames, config.image_size)
         obj_frames = [_frames(p, config.n_frames, config.image_size) for p in config.edited_contorl_frame_path]
         bg_frames = _frames(config.edited_contorl_frame_path_background, config.n_frames, config.image_size)
         ddim_scheduler.set_timesteps(config.n_steps)
@@ -273,13 +301,22 @@ def main(template_config, configs_list, device, synthetic=False, dedup_sources=F
                       main_first_image=[main_1st if same_1st(c) else first(c) for c in variants],
                       main_image_list=[main_frames if same_main(c) else
                                        _frames(c.edited_contorl_frame_path_main, c.n_frames, c.image_size) for c in variants])
+        if compose:
+            kw.update(main_first_image=None, main_image_list=None, **compose)
         for od in output_dirs:
             os.makedirs(od, exist_ok=True)
+
+        def sample(output_type):
+            res = pipe.sample_with_pnp_pipeline_with_edit_prompt_extraction_with_attn_injection(output_type=output_type, **kw)
+            if res.main_frames is not None:
+                for k, od in enumerate(output_dirs):
+                    _write_main_frames(res.main_frames[k], od)
+            return res.frames
         try:
-            videos = pipe.sample_with_pnp_pipeline_with_edit_prompt_extraction_with_attn_injection(output_type=out_type, **kw).frames
+            videos = sample(out_type)
         except NotImplementedError as e:  # no VAE decoder on this path: keep the composed latents
             logger.warning(f"composition decoded to latents only ({e})")
-            lat = pipe.sample_with_pnp_pipeline_with_edit_prompt_extraction_with_attn_injection(output_type="latent", **kw).frames
+            lat = sample("latent")
             if variants is None:
                 torch.save(lat.cpu(), os.path.join(output_dirs[0], "video_latents.pt"))
             else:

@@ -522,6 +522,21 @@ int mvoc_pnp_blend_scatter_nchw_bilinear(const mvoc_pnp_desc* d, int32_t nsrc, c
 int mvoc_gather_planes_bilinear_f16(const void* src, void* dst, int32_t nplane, int32_t frames, int32_t h, int32_t w,
                                     const int32_t* taps, void* stream);
 
+/* The main conditioning frames of a composition: the background with every object alpha-blended over it, sampled
+ * through a tap table at the IMAGE site, in integers only.  bg uint8 [frames][h][w][3], objs uint8 [nobj][frames][h][w][3], alpha
+ * uint8 [nobj][frames][h][w] (straight alpha, 0..255), out uint8 [frames][h][w][3], all contiguous on the device; `taps`: DEVICE
+ * int32 [nobj][frames][h * w][2], 8-byte aligned (an entry is read as one int2), in the form above: word 0 names the upper-left tap,
+ * -1 where absent; of word 1's two 9-bit weight fields a value above 256 counts as 256.  That clamp is this entry's alone -- the fp16
+ * entries above read the 9 bits as they are and do not clamp, so the two decodings agree for q <= 256, which is every table the
+ * builders make; here it keeps every sample a byte and all arithmetic inside int32 for ANY table.  Per pixel and channel, o = bg; for j = 0 .. nobj-1 (later objects in front), with
+ *   S(v) = ((v00*(256-qx) + v01*qx)*(256-qy) + (v10*(256-qx) + v11*qx)*qy + 32768) >> 16    (a tap outside the plane: 0)
+ *   a = S(alpha_j);  o = (o*(255-a) + S(objs_j)*a + 127) / 255
+ * A tap outside the plane issues its loads at the plane's pixel 0 and is masked to 0: every int32 pair is valid.  Reports
+ * frames*h*w * (6 + 12*nobj) bytes (MVOC_FAM_MISC).  Refuses, in this order, with nothing written: a null operand (-1), out equal
+ * to an input (-1), nobj outside [1, 16] or a non-positive dim (-1), h or w >= 65535 (-2), h * w >= 2^31 (-2), a grid too large (-2). */
+int mvoc_collage_rgb_u8(const void* bg, const void* objs, const void* alpha, void* out, int32_t nobj, int32_t frames, int32_t h,
+                        int32_t w, const int32_t* taps, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Loop glue on [B,4,F,h,w] fp16 latents, BIT-EXACT vs the reference's eager fp16 op chain.
  *   cfg + DDIM / inverse-DDIM update (pipeline_i2vgen_xl.py:1187-1199, 1713-1731, 1967-1984;

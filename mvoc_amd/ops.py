@@ -1090,6 +1090,96 @@ def warp_planes_bilinear(src, taps, out=None):
                         name="taps")
 
 
+# ---- the main conditioning frames, composed from the placed objects at the image site -------------------------------
+COLLAGE_FILTERS = (None, "nearest", "bilinear")  # what ``obj_transform_filter`` resolves to, and its two spellings of nearest
+COLLAGE_MAX_OBJECTS = 16
+
+
+def _level_nearest_words(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw):
+    """the nearest form of a tap row: ``pack_taps`` of the pixel ``level_warp_map`` names as the upper-left tap with zero weights
+    (-1 where the object is absent), as an int32 tensor [H * W, 2] -- without the detour through lists where the int64 form serves"""
+    args = _warp_args(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw)
+    i64, coords = _warp_coords("collage_taps", warp_numerator_bound(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw), None, "a numerator", args)
+    if not i64:
+        px = level_warp_map(dy, dx, m, den, ay2, ax2, H, W, Lh, Lw, "py")
+        return torch.tensor(pack_taps([(s // W, s % W, 0, 0) if s >= 0 else (-2, -2, 0, 0) for s in px], H, W), dtype=torch.int32)
+    Ny, Dy, Nx, Dx = coords
+    sy, sx = _fdiv(Ny, Dy), _fdiv(Nx, Dx)
+    inside = (sy >= 0) & (sy < H) & (sx >= 0) & (sx < W)
+    w0 = torch.where(inside, ((sy + 1) << 16) | (sx + 1), torch.full_like(sy, -1))
+    w0 = torch.where(w0 >= 1 << 31, w0 - (1 << 32), w0).reshape(-1)
+    return torch.stack([w0, torch.zeros_like(w0)], dim=-1).to(torch.int32)
+
+
+def _collage_rows(warp, height, width, mask_h, mask_w, filter):
+    """-> (rows, index): the DISTINCT tap rows of ``warp`` at the site, each an int32 [height * width, 2] tensor computed once, and
+    per object the row of every frame as indices into them"""
+    _check_frames("collage_taps", warp)
+    if filter not in COLLAGE_FILTERS:
+        raise RuntimeError(f"collage_taps: filter {filter!r} is not one of None, 'nearest', 'bilinear'")
+    if height >= TAP_SITE_LIMIT or width >= TAP_SITE_LIMIT:
+        raise RuntimeError(f"collage_taps: {height} x {width}: a site of {TAP_SITE_LIMIT} rows or columns or more does not fit the "
+                           "16-bit tap fields")
+    words = _level_tap_words if filter == "bilinear" else _level_nearest_words
+    rows = []
+
+    def level(*a):
+        rows.append(words(*a, height, width, mask_h, mask_w))
+        return len(rows) - 1
+    return rows, _per_frame(warp, level)
+
+
+def collage_taps(warp, H, W, mask_h, mask_w, filter=None):
+    """``warp`` (the value of ``warp_maps``) -> the tap table of the collage at the image site H x W under the mask_h x mask_w latent
+    grid: an int32 CPU tensor [nobj, F, H * W, 2], one computation per distinct frame value of an object.  "bilinear": ``warp_taps``
+    bit for bit; None / "nearest": degenerate taps -- the upper-left tap is the pixel ``level_warp_map`` names, both weights 0.
+    When no object changes along the clip the frame axis is a stride-0 view of the one row per object (no F copies)."""
+    rows, index = _collage_rows(warp, H, W, mask_h, mask_w, filter)
+    if all(len(set(obj)) == 1 for obj in index):
+        return torch.stack([rows[obj[0]] for obj in index])[:, None].expand(len(index), len(index[0]), H * W, 2)
+    return torch.stack(rows)[torch.tensor(index)].contiguous()
+
+
+def collage_tap_table(warp, H, W, mask_h, mask_w, filter, device):
+    """the device table ``collage`` reads: ``collage_taps`` as a contiguous int32 [nobj, F, H * W, 2].  Only the DISTINCT rows are
+    built on the host and uploaded; the frames that share a row are spread on the device"""
+    rows, index = _collage_rows(warp, H, W, mask_h, mask_w, filter)
+    return torch.stack(rows).to(device)[torch.tensor(index, device=device)].contiguous()
+
+
+def collage(bg, objs, alpha, taps, out=None):
+    """the background with every object alpha-blended over it through a tap table, in integers (the rule is stated
+    at mvoc_collage_rgb_u8 in include/mvoc_hip.h).  ``bg`` uint8 [F, H, W, 3], ``objs`` uint8 [nobj, F, H, W, 3], ``alpha`` uint8
+    [nobj, F, H, W], ``taps`` int32 [nobj, F, H * W, 2] (``collage_tap_table``), all contiguous on the device -> uint8 [F, H, W, 3]"""
+    _chk(bg, "bg", torch.uint8), _chk(objs, "objs", torch.uint8), _chk(alpha, "alpha", torch.uint8), _chk(taps, "taps", torch.int32)
+    if bg.dim() != 4 or bg.shape[-1] != 3 or not bg.is_contiguous():
+        raise RuntimeError(f"collage: bg must be contiguous [F, H, W, 3], got {tuple(bg.shape)}")
+    frames, h, w = bg.shape[:3]
+    if objs.dim() != 5 or tuple(objs.shape[1:]) != tuple(bg.shape) or not objs.is_contiguous():
+        raise RuntimeError(f"collage: objs must be contiguous [nobj, F = {frames}, H = {h}, W = {w}, 3], got {tuple(objs.shape)}")
+    nobj = objs.shape[0]
+    if tuple(alpha.shape) != (nobj, frames, h, w) or not alpha.is_contiguous():
+        raise RuntimeError(f"collage: alpha must be contiguous [nobj = {nobj}, F = {frames}, H = {h}, W = {w}], got {tuple(alpha.shape)}")
+    if tuple(taps.shape) != (nobj, frames, h * w, 2) or not taps.is_contiguous():
+        raise RuntimeError(f"collage: taps must be a contiguous int32 [nobj = {nobj}, F = {frames}, h * w = {h * w}, 2] table, "
+                           f"got {tuple(taps.shape)}")
+    if taps.data_ptr() % 8:
+        raise RuntimeError(f"collage: taps must be 8-byte aligned (the kernel reads a table entry as one int2), got an address "
+                           f"ending in {taps.data_ptr() % 8}")
+    if out is None:
+        out = torch.empty_like(bg)
+    _chk(out, "out", torch.uint8)
+    if out.shape != bg.shape or not out.is_contiguous():
+        raise RuntimeError("collage: out must be contiguous and of bg's shape")
+    lo, hi = out.data_ptr(), out.data_ptr() + out.numel()
+    for name, t in (("bg", bg), ("objs", objs), ("alpha", alpha), ("taps", taps)):
+        if t.data_ptr() < hi and lo < t.data_ptr() + t.numel() * t.element_size():
+            raise RuntimeError(f"collage: out overlaps {name} (in place is not supported)")
+    check(lib.mvoc_collage_rgb_u8(bg.data_ptr(), objs.data_ptr(), alpha.data_ptr(), out.data_ptr(), nobj, frames, h, w,
+                                  taps.data_ptr(), _stream()), "collage_rgb_u8")
+    return out
+
+
 def ddim_step(x, v_cond, coef_dev, v_uncond=None, out=None):
     """coef_dev: fp32 device tensor {sqrt(a_t), sqrt(1-a_t), sqrt(a_prev), sqrt(1-a_prev), guidance_scale}; a [K, 5] tensor
     with K > 1 updates K variants in one launch: x, v_cond, v_uncond, out are then [K, ...] and variant k takes row k."""

@@ -34,9 +34,11 @@ H16 = torch.float16
 
 
 class PipelineOutput:
-    def __init__(self, frames=None, inverted_latents=None):
+    def __init__(self, frames=None, inverted_latents=None, main_frames=None, collage_info=None):
         self.frames = frames
         self.inverted_latents = inverted_latents
+        self.main_frames = main_frames  # compose_main_images: per variant the composed conditioning frames
+        self.collage_info = collage_info  # ... and what composing them took (``compose_main_frames``)
 
 
 class SyntheticConditioner:
@@ -477,6 +479,52 @@ def resolve_variant_obj_transforms(variant_obj_transforms, nvar, n_obj, num_fram
         zero = tuple(((0, 0),) * num_frames for _ in range(n_obj))
         return None, tuple(zero if pl is None else pl for pl, _ in downs), None, None
     return None, None, None, tuple(fulls)
+
+
+def collage_warps(placed, nvar, n_obj, num_frames, lat_h, lat_w):
+    """what the resolvers of the sampling call returned (``placed``: placement / variant_placements / transform /
+    variant_transforms / warp, at most one not None) -> the warps the main conditioning frames are composed under:
+    a list of ONE warp for a mode shared by the variants (or none), of K = ``nvar`` for a per-variant mode; each a value
+    ``ops.collage_taps`` takes, per object (ay2, ax2, ((myy, myx, mxy, mxx, den, dy, dx) per frame)) on the ``lat_h`` x ``lat_w``
+    grid.  A placement is the identity matrix with its (dy, dx); a transform goes through ``_warp_of`` with the zero rotation; a
+    warp is itself; no mode is the identity."""
+    identity = lambda offs: (int(lat_h), int(lat_w), tuple((1, 0, 0, 1, 1, int(dy), int(dx)) for dy, dx in offs))
+    of_placement = lambda pl: tuple(identity(offs) for offs in pl)
+    of_transform = lambda tr: tuple(_warp_of(full, ((WARP_DEN, 0),) * num_frames) for full in tr)
+    get = lambda key: placed.get(key) if placed else None
+    if get("warp") is not None:
+        return [tuple(placed["warp"])]
+    if get("variant_transforms") is not None:
+        warps = [of_transform(tr) for tr in placed["variant_transforms"]]
+    elif get("transform") is not None:
+        return [of_transform(placed["transform"])]
+    elif get("variant_placements") is not None:
+        warps = [of_placement(pl) for pl in placed["variant_placements"]]
+    elif get("placement") is not None:
+        return [of_placement(placed["placement"])]
+    else:
+        return [tuple(identity(((0, 0),) * num_frames) for _ in range(n_obj))]
+    if len(warps) != nvar:
+        raise ValueError(f"collage_warps: {len(warps)} per-variant values for {nvar} variants")
+    return warps
+
+
+def _frames_rgb_u8(frames, num_frames, height, width, what):
+    """a list of ``num_frames`` images -> uint8 [F, height, width, 3] (RGB); a frame of another size is a ValueError: the call
+    does not resize"""
+    import numpy as np
+    frames = list(frames)
+    if len(frames) != num_frames:
+        raise ValueError(f"compose_main_images: {what} has {len(frames)} frames, the clip {num_frames}")
+    out = []
+    for i, im in enumerate(frames):
+        if not hasattr(im, "convert"):
+            raise ValueError(f"compose_main_images: {what}, frame {i} is not an image ({type(im).__name__})")
+        if tuple(im.size) != (width, height):
+            raise ValueError(f"compose_main_images: {what}, frame {i} is {im.size[0]} x {im.size[1]}, the call {width} x {height} "
+                             "(width x height; the call does not resize)")
+        out.append(np.asarray(im.convert("RGB"), dtype=np.uint8))
+    return torch.from_numpy(np.stack(out))
 
 
 def crosses_gemm_offset_line(nb, frames, h, w, width0):
@@ -1179,6 +1227,58 @@ class I2VGenXLPipeline:
         g()
 
     @torch.no_grad()
+    def compose_main_frames(self, placed, nvar, n_obj, num_frames, height, width, background_image_list, objs_image_list,
+                            obj_mask=None, obj_alpha=None, warp_filter=None):
+        """the main conditioning frames of the sampling call, composed on the device: the background frames with
+        every object's frames alpha-blended over them (later objects in front) under the warps ``collage_warps`` makes of
+        ``placed``, at the site (height, width) under the latent grid, sampled by ``warp_filter`` (None: nearest) -> (per variant
+        a list of ``num_frames`` RGB images, info).  One kernel launch per DISTINCT warp; variants that share a warp share the
+        very same image objects.  ``info``: launches, table_bytes (device bytes of the tap tables), table_rows_host (the
+        distinct rows built on the host and uploaded) and seconds (the stage's synchronised wall-clock)."""
+        import time
+        import numpy as np
+        from PIL import Image
+        from .utils import mask_alpha_frames
+        if not 1 <= n_obj <= ops.COLLAGE_MAX_OBJECTS:
+            raise ValueError(f"compose_main_images: {n_obj} objects, the collage takes 1 to {ops.COLLAGE_MAX_OBJECTS}")
+        if len(objs_image_list) != n_obj:
+            raise ValueError(f"compose_main_images: objs_image_list holds {len(objs_image_list)} clips for {n_obj} objects")
+        torch.cuda.synchronize(self.device)
+        t0 = time.perf_counter()
+        bg = _frames_rgb_u8(background_image_list, num_frames, height, width, "background_image_list")
+        objs = torch.stack([_frames_rgb_u8(fr, num_frames, height, width, f"objs_image_list[{j}]") for j, fr in enumerate(objs_image_list)])
+        if obj_alpha is not None:
+            if len(obj_alpha) != n_obj:
+                raise ValueError(f"compose_main_images: obj_alpha holds {len(obj_alpha)} arrays for {n_obj} objects")
+            alphas = [a.cpu() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a)) for a in obj_alpha]
+        elif obj_mask is not None:
+            alphas = [torch.from_numpy(mask_alpha_frames(p, num_frames)) for p in obj_mask]
+        else:
+            raise ValueError("compose_main_images=True needs the objects' image-size masks: obj_mask paths or obj_alpha "
+                             "(obj_masks_tensors are at latent size)")
+        for j, a in enumerate(alphas):
+            if a.dtype != torch.uint8 or tuple(a.shape) != (num_frames, height, width):
+                raise ValueError(f"compose_main_images: the alpha of object {j} is {a.dtype} {tuple(a.shape)}, the call needs uint8 "
+                                 f"[F = {num_frames}, height = {height}, width = {width}]")
+        lat_h, lat_w = height // self.vae_scale_factor, width // self.vae_scale_factor
+        warps = collage_warps(placed, nvar, n_obj, num_frames, lat_h, lat_w)
+        dev = self.device
+        bg, objs, alpha = bg.to(dev), objs.contiguous().to(dev), torch.stack(alphas).contiguous().to(dev)
+        built, info = {}, {"launches": 0, "table_bytes": 0, "table_rows_host": 0}
+        for warp in warps:
+            if warp in built:
+                continue
+            taps = ops.collage_tap_table(warp, height, width, lat_h, lat_w, warp_filter, dev)
+            out = ops.collage(bg, objs, alpha, taps).cpu().numpy()
+            built[warp] = [Image.fromarray(fr) for fr in out]
+            info["launches"] += 1
+            info["table_bytes"] += taps.numel() * 4
+            info["table_rows_host"] += sum(len(set(tuple(fr) for fr in obj[2])) for obj in warp)
+        frames = [built[w] for w in warps]
+        info["seconds"] = time.perf_counter() - t0  # (the frames came back through synchronising copies)
+        return (frames * nvar if len(frames) == 1 else frames), info
+
+    @torch.no_grad()
     def sample_with_pnp_pipeline_with_edit_prompt_extraction_with_attn_injection(
             self, prompt=None, main_first_image=None, main_image_list=None, background_first_image=None,
             background_image_list=None, objs_first_image=None, objs_image_list=None, height=704, width=1280, target_fps=16,
@@ -1188,7 +1288,8 @@ class I2VGenXLPipeline:
             fusion_steps=(0, 3), ddim_init_latents_t_idx=1, ddim_inv_prompt=None, obj_mask=None, obj_width_height=None,
             obj_ddim_latents_idx_offset=None, obj_random_noise_fusion=False, random_noise_ratio=0.0,
             bg_inv_latents_path=None, obj_ddim_latents_path=None, obj_masks_tensors=None, obj_offsets=None,
-            variant_obj_offsets=None, obj_transforms=None, variant_obj_transforms=None, obj_transform_filter=None):
+            variant_obj_offsets=None, obj_transforms=None, variant_obj_transforms=None, obj_transform_filter=None,
+            compose_main_images=False, obj_alpha=None):
         """PnP composition sampling.  ``obj_mask``: list of mask paths (preprocessed by ``mvoc_amd.utils.mask_preprocess``)
         or pass ``obj_masks_tensors`` = list of (float [1,4,F,h,w], bool [1,4,F,h,w]) directly.
 
@@ -1224,8 +1325,23 @@ class I2VGenXLPipeline:
         ``obj_transform_filter``: None or "nearest" -- exactly the call without it; "bilinear" (with
         ``obj_transforms`` only) -- scaled, mirrored and turned objects are sampled bilinearly (fixed-point weights, an exact fp16
         chain) at every injection site, in the soft masks and in the fusion steps; a translation-only call stays the
-        ``obj_offsets`` call, an identity call the call without the argument."""
+        ``obj_offsets`` call, an identity call the call without the argument.
+
+        ``compose_main_images``: True -- ``main_first_image`` and ``main_image_list`` stay None and the call
+        builds them on the device: the background frames with the object frames alpha-blended over them under the call's own
+        placement (``compose_main_frames``; per variant under ``variant_obj_offsets`` / ``variant_obj_transforms``), sampled by
+        ``obj_transform_filter``.  The alphas are the image-size masks behind the ``obj_mask`` paths or ``obj_alpha``, a list of
+        uint8 [F, height, width] arrays (for callers that pass ``obj_masks_tensors``).  The frames must be ``width`` x ``height``
+        already; not with a frame shard.  The composed frames come back as ``.main_frames`` (per variant a list of images).
+        False: exactly the call without the argument."""
         from .utils import mask_preprocess
+        if compose_main_images:
+            for name, value in (("main_first_image", main_first_image), ("main_image_list", main_image_list)):
+                if value is not None:
+                    raise ValueError(f"compose_main_images=True builds {name} from the sources: pass None, not {type(value).__name__}")
+            if obj_mask is None and obj_alpha is None:
+                raise ValueError("compose_main_images=True needs the objects' image-size masks: obj_mask paths or obj_alpha "
+                                 "(obj_masks_tensors are at latent size)")
         # ---- the variants of this call (one with scalar arguments: the batch, kernels and launches of a single composition)
         m_rep = int(num_videos_per_prompt)
         if m_rep < 1:
@@ -1303,6 +1419,14 @@ class I2VGenXLPipeline:
         for m in PLACEMENT_MODES:
             if placed[m.attr] is not None and self.unet.shard is not None:
                 raise RuntimeError(frame_shard_refusal(m.arg + " do", m.mover))
+        main_frames = collage_info = None
+        if compose_main_images:
+            if self.unet.shard is not None:
+                raise RuntimeError(frame_shard_refusal("compose_main_images does", "collage"))
+            main_frames, collage_info = self.compose_main_frames(
+                placed, nvar, n_obj, num_frames, height, width, background_image_list, objs_image_list, obj_mask, obj_alpha, warp_filter)
+            # (variants that share a warp hold the SAME objects: one VAE draw and one vision-tower pass below)
+            mains_first, mains_list = [fr[0] for fr in main_frames], list(main_frames)
         # source de-duplication: roles showing the same image share ONE draw of the VAE posterior (prepare_image_latents samples
         # per role, :860-890) and one vision-tower pass -- else identical frames would give every role its own image latents and
         # no two roles could share a chunk (make_composition_state)
@@ -1412,4 +1536,4 @@ class I2VGenXLPipeline:
             self.composition_step(st, t, bg, objs, table[index[t]], fuse)
         latents = st["latents"].clone()
         frames = latents if output_type == "latent" else self._to_video(latents, output_type)
-        return PipelineOutput(frames=frames) if return_dict else (frames,)
+        return PipelineOutput(frames=frames, main_frames=main_frames, collage_info=collage_info) if return_dict else (frames,)

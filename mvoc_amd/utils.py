@@ -118,6 +118,21 @@ def _one_mask(path, downscale):
     return u8.to(torch.float32).div_(255.0), u8 > 10
 
 
+def mask_alpha_frames(mask, frames):
+    """the image-size masks behind ``mask_preprocess``, undecimated: uint8 [F, H, W] ("L" images) by its listing rule -- a
+    directory gives one mask per frame (``*.png`` sorted by their number, the first ``frames``), a single file is repeated"""
+    if osp.isdir(mask):
+        paths = glob(osp.join(mask, "*.png"))
+        paths.sort(key=lambda p: int(osp.basename(p).split(".")[0]))
+        imgs = [np.asarray(Image.open(p).convert("L")) for p in paths[:frames]]
+    else:
+        imgs = [np.asarray(Image.open(mask).convert("L"))] * frames
+    if len(imgs) != frames or len({im.shape for im in imgs}) != 1:
+        raise ValueError(f"mask_alpha_frames: {mask}: {len(imgs)} masks of the sizes {sorted({im.shape for im in imgs})} "
+                         f"for {frames} frames of one size")
+    return np.stack(imgs)
+
+
 def mask_preprocess(mask, device, dtype, batch_size, channel, frames, downscale=8):
     """-> (float [b,c,F,h,w] in ``dtype``, bool [b,c,F,h,w]); a directory gives one mask per frame
     (``utils.py:113-154``), a single file is repeated over frames.  On a GPU device the resize / threshold / scaling run

@@ -31,6 +31,9 @@ in the format of --transform -- the variants' `transform` key; an
 With --sequential the K single jobs each take their variant's transform as `obj_transform`.
 --transform-filter bilinear (opt-in, needs --transform): the entry's `obj_transform_filter` -- scaled, mirrored and
 turned objects are sampled bilinearly; the result line then names the filter (`obj_transform_filter`).  Not with --variant-transform.
+--compose-main (opt-in): the entry's `compose_main` -- the sampling call composes the main conditioning frames from
+the background and object frames under the entry's own placement instead of loading the edited first frame and the main control
+frames; the result line then holds `compose_main`: the collage stage's own wall-clock, its launches and the bytes of its tap tables.
 
 --shared-source (opt-in): the shape of MVOC's own demo entries, where the background and both objects point at ONE inversion
 directory and the same control frames.  One clip is inverted, then the composition runs with source de-duplication off and then
@@ -307,6 +310,7 @@ class StageTimer:
 
     def __init__(self, pl):
         self.pl, self.sample_s, self.decode_s, self.steps = pl, 0.0, 0.0, []
+        self.collage_info = None  # what the sampling call reports about its collage stage (--compose-main)
         self._orig = (getattr(pl.I2VGenXLPipeline, self.NAME), pl.I2VGenXLPipeline._to_video, pl.I2VGenXLPipeline.composition_step)
 
     def __enter__(self):
@@ -317,7 +321,9 @@ class StageTimer:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             try:
-                return sample_fn(self, *a, **kw)
+                out = sample_fn(self, *a, **kw)
+                timer.collage_info = getattr(out, "collage_info", None)
+                return out
             finally:
                 torch.cuda.synchronize()
                 timer.sample_s += time.perf_counter() - t0
@@ -452,7 +458,7 @@ def parse_variant_transform(text, variants):
 
 
 def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, thresholds=None, sequential=False, place=None,
-                 variant_place=None, transform=None, variant_transform=None, transform_filter=None):
+                 variant_place=None, transform=None, variant_transform=None, transform_filter=None, compose_main=False):
     """K prompts and seeds over the boat_surf-shaped job (three distinct sources), one composition loop (composite.py `variants`).
     ``thresholds``: K values of pnp_spatial_attn_t, one per variant (the variants' `pnp` key); ``sequential``: after
     the one loop, the same K compositions one by one (single entries with the flat threshold) for the comparison."""
@@ -508,9 +514,14 @@ def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, threshol
         centry["obj_transform"] = [dict(t) for t in transform]
     if transform_filter is not None:  # how the transformed objects are sampled: an entry key next to obj_transform
         centry["obj_transform_filter"] = transform_filter
+    if compose_main:  # the main conditioning frames composed by the call: an entry key, the edited frames are not loaded
+        centry["compose_main"] = True
     with StageTimer(pl) as timer:
         composite.main(ct, [centry], dev, synthetic=True)
     res = timer.result()
+    if compose_main:  # the collage stage alone (frames to the device, tap tables, kernel, frames back as images), as the call reports it
+        info = dict(timer.collage_info)
+        res["compose_main"] = dict(info, collage_s=round(info.pop("seconds"), 3))
     out_root = os.path.join(root, "Results", "demo", "i2vgen-xl", "bg_clip", "out")
     suffixes = sorted(os.listdir(out_root))  # (per-variant thresholds: every variant under the suffix of its own thresholds)
     files, where = {}, {}
@@ -548,6 +559,8 @@ def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, threshol
                 e["obj_transform"] = [dict(o) for o in variant_transform[k]]
             if thresholds is not None:
                 e["pnp_spatial_attn_t"] = float(thresholds[k])
+            if compose_main:
+                e["compose_main"] = True
             with StageTimer(pl) as t1:
                 composite.main(ct, [e], dev, synthetic=True)
             seq.append(t1.result())
@@ -592,8 +605,12 @@ if __name__ == "__main__":
                          "`transform` key); an empty item leaves that variant untransformed")
     ap.add_argument("--transform-filter", type=str, default=None, choices=("nearest", "bilinear"),
                     help="with --transform: how the transformed objects are sampled (`obj_transform_filter`; default nearest)")
+    ap.add_argument("--compose-main", action="store_true",
+                    help="compose the main conditioning frames from the sources under the entry's placement (`compose_main`)")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
+    if a.compose_main and not a.variants:  # the option alone reaches run_variants as well (K = 1)
+        a.variants = 1
     if a.variants or a.place or a.variant_place or a.transform or a.variant_transform or a.transform_filter:
         th = None if a.variant_thresholds is None else [float(x) for x in a.variant_thresholds.split(",")]
         place = None if a.place is None else parse_place(a.place)
@@ -601,7 +618,7 @@ if __name__ == "__main__":
         transform = None if a.transform is None else parse_transform(a.transform)
         vtransform = None if a.variant_transform is None else parse_variant_transform(a.variant_transform, a.variants)
         print(json.dumps(run_variants(a.frames, a.size, a.steps, a.keep, a.variants or 1, th, a.sequential, place, vplace, transform,
-                                      vtransform, a.transform_filter)), flush=True)
+                                      vtransform, a.transform_filter, a.compose_main)), flush=True)
     else:
         fn = run_shared_source if a.shared_source else run
         print(json.dumps(fn(a.frames, a.size, a.steps, a.keep)), flush=True)
