@@ -562,6 +562,34 @@ int mvoc_latent_fusion_variants_f16(const void* latents, const void* bg, const v
 
 /* ---------------------------------------------------------------------------------------------
  * Stem / small ops (pipeline_i2vgen_xl.py:166-290, 351-357).
+ *
+ * Extents (enforced by tests/test_stem_contract_gpu.py for the nineteen entries of this section, of the VAE, mask and CLIP sections
+ * below and mvoc_permute_rows_f16: one thread per output, walked at 1, 255, 256, 257 and 513 work items on allocations whose
+ * undescribed elements are NaN).  Common to all of them:
+ *   - only the elements named per entry influence a result; the columns of a pitched row past its c channels, a table the form does
+ *     not index, and whatever lies around any operand never do, whatever they hold;
+ *   - no byte outside the described output is written: not the other channels of an ldo- or ld-pitched row (columns below coff and at
+ *     or past coff + c keep what they held), nothing in front of or behind the operand, and no input operand;
+ *   - operands need the alignment of their element (2 bytes fp16, 4 bytes fp32 / int32) unless the entry says 16 bytes;
+ *   - the return value is 0, -1 (a NULL operand, a non-positive extent, or the precondition the entry names) or -3 (launch failure),
+ *     with the text in mvoc_last_error(); a refused call launches nothing and writes nothing.
+ * Per entry:
+ *   timestep_embedding  reads t[nb] (fp32); writes out[nb][dim], out[b][k] = cos, out[b][dim/2 + k] = sin of t[b] * 10000^(-k / (dim/2)),
+ *                       evaluated in fp32 and rounded once.  -1: dim odd.
+ *   act                 reads x[n], writes out[n]: act = MVOC_ACT_SILU x / (1 + exp(-x)), MVOC_ACT_GELU 0.5 x (1 + erf(x / sqrt 2)), in
+ *                       fp32, rounded once (within one fp16 ulp of the fp64 value, GELU plus 2^-22 |x|).
+ *   add                 reads a[n], b[n], writes out[n]: the exact sum rounded once.
+ *   conv3x3_small       reads x[nimg][h][wd][cin], w[cout][3][3][cin], bias[cout] (NULL: none); writes out[nimg][ho][wo][cout], ho =
+ *                       (h - 1) / stride + 1, wo likewise; the tap (ky, kx) of output (oy, ox) is x[oy stride + ky - 1][ox stride + kx - 1],
+ *                       zero outside the image; fp32 sum + bias rounded to fp16, then SiLU (silu != 0) rounded again.  -1: stride not 1 or 2.
+ *   adaptive_avgpool    reads x[nimg][h][w][c], writes out[nimg][oh][ow][c]: the mean over rows [floor(oy h / oh), ceil((oy + 1) h / oh))
+ *                       and the columns likewise (torch's AdaptiveAvgPool2d windows; oh > h repeats rows): fp32 sum / fp32 count, rounded once.
+ *   ncfhw_to_tokens     reads x[b][c][f][hw]; writes out[b f hw][ldo] in the columns [coff, coff + c) only.  -1: coff < 0, ldo < coff + c.
+ *   tokens_to_ncfhw     reads x[b f hw][ld] in the columns [0, c) only; writes out[b][c][f][hw].  -1: ld < c.
+ *   temporal_encoder4   reads x[b f hw][4] and the 288 fp16 of params; writes out[b f hw][ldo] in the columns [coff, coff + 4) only; the row
+ *                       of pixel (bi, p), frame i depends on the f rows x[bi][.][p] alone.  Rounded to fp16 after the LayerNorm, each of
+ *                       q / k / v, the attention output, to_out + bias, the residual sum, FF1 + bias, GELU, FF2 + bias and the last sum
+ *                       (softmax and sums in fp32).  -1: coff < 0, ldo < coff + 4.
  * ------------------------------------------------------------------------------------------- */
 /* sinusoidal Timesteps(dim, flip_sin_to_cos=True, shift 0): out[b] = [cos | sin] rounded to fp16; t fp32 on device */
 int mvoc_timestep_embedding_f16(const float* t_dev, int32_t nb, int32_t dim, void* out, void* stream);
@@ -592,6 +620,17 @@ int mvoc_temporal_encoder4_f16(const void* x, const void* params, void* out, int
  * prepare_image_latents, :893-920 encode_vae_video -> diffusers AutoencoderKL).  The convolutions, GroupNorms and the
  * mid-block attention's projections run through the entries above (mvoc_gemm_f16 incl. pad_mode = 1 for the encoder's
  * Downsample2D(padding=0), mvoc_groupnorm_f16); what they need in addition:
+ *
+ * Extents (enforced by tests/test_stem_contract_gpu.py; the common rules stand above, under "Stem / small ops"):
+ *   conv1x1_small    reads x[rows][cin], w[cout][cin], bias[cout] (NULL: none); writes out[rows][cout]: fp32 sum + bias, rounded once.
+ *                    -1: cin or cout above 64.
+ *   softmax_rows     reads and writes x[rows][cols] in place and nothing else; exp and sum in fp32, one rounding (a result is the fp64
+ *                    softmax rounded to fp16, or its fp16 neighbour where the fp32 error reaches across a rounding boundary).  x must be
+ *                    16-byte aligned (rows move as 16-byte vectors).  -1: cols % 8 != 0, x misaligned.
+ *   gaussian_sample  reads mean[n], logvar[n], noise[n], writes out[n]; a NaN logvar gives NaN (torch.clamp keeps it).
+ *   scale            reads x[n], writes out[n] = fp16(fp32(float(scale) * x)).
+ *   image_to_tokens  reads x[n][c][hw], writes out[n hw][c].
+ *   tokens_to_image  reads x[n hw][ld] in the columns [0, c) only, writes out[n][c][hw].  -1: ld < c.
  * ------------------------------------------------------------------------------------------- */
 /* 1x1 conv over a handful of channels on channels-last rows: out[r][o] = sum_c x[r][c] w[o][c] + bias[o]
  * (AutoencoderKL.quant_conv 8 -> 8, post_quant_conv 4 -> 4); cin, cout <= 64 */
@@ -615,6 +654,13 @@ int mvoc_tokens_to_image_f16(const void* x, void* out, int32_t n, int32_t c, int
  * uint8, then vertical) reproduced bit for bit from host-built coefficient tables (per output index {xmin, n} and n int32
  * weights, row pitch ksize), then float = v/255 in fp16 and bool = v > 10 (cv.threshold(.., 10, 255) / 255 -> bool).
  *   in [n][H][W] u8, tmp [n][H][w] u8, out [n][h][w] u8;  float_mask fp16 / bool_mask u8 of the same element count
+ *
+ * Extents (enforced by tests/test_stem_contract_gpu.py; the common rules stand under "Stem / small ops"):
+ *   mask_resize_u8  reads in[n][H][W], bounds_h[w][2], kk_h[w][ksize_h] (of row xx its first bounds_h[xx][1] weights), bounds_v[h][2],
+ *                   kk_v[h][ksize_v]; writes tmp[n][H][w] (the horizontal pass, PIL's resize to (w, H)) and out[n][h][w], both bit for
+ *                   bit PIL's, the clip to 0 and 255 included.  The tables must come from mvoc_amd.utils.pil_bicubic_tables(W, w) and
+ *                   (H, h): a window that leaves [0, W) or [0, H) is not checked.
+ *   mask_finish     reads v[n]; writes float_mask[n] = fp16(fp32(v) / 255) and bool_mask[n] = v > 10 (1 or 0).
  * ------------------------------------------------------------------------------------------- */
 int mvoc_mask_resize_u8(const void* in, void* tmp, void* out, int32_t n, int32_t H, int32_t W, int32_t h, int32_t w,
                         const int32_t* bounds_h, const int32_t* kk_h, int32_t ksize_h, const int32_t* bounds_v,
@@ -629,6 +675,15 @@ int mvoc_mask_finish(const void* v, void* float_mask, void* bool_mask, int64_t n
  *                 (k = (c, py, px) like Conv2d's weight.view(N, -1); columns >= 3*patch^2 are zero)
  *   clip_embed  : out[row] = src(row) + pos[row % t]; src = table[ids[row]] (text: token + position embedding), or with
  *                 ids == NULL the class embedding at t == 0 and patch row (row/t)*(t-1) + (row%t) - 1 otherwise (vision)
+ *
+ * Extents (enforced by tests/test_stem_contract_gpu.py; the common rules stand under "Stem / small ops"):
+ *   clip_patches  reads pixels[nimg][3][size][size]; writes out[nimg (size/patch)^2][kpad], every column: the columns at and past
+ *                 3 patch^2 are WRITTEN as zero, not left.  -1: size % patch != 0, kpad < 3 patch^2.
+ *   clip_embed    reads pos[t][c]; with ids: ids[rows] and the rows of table[.][c] they name (0 <= ids[row] < the table's rows is the
+ *                 caller's promise, not checked), cls is not read; with ids == NULL: cls[c] and table[(rows / t)(t - 1)][c], which at
+ *                 t == 1 is never read (the pointer must still be non-NULL).  Writes out[rows][c], the exact sum rounded once.  table,
+ *                 cls, pos and out must be 16-byte aligned (rows move as 16-byte vectors).  -1: c % 8 != 0, rows % t != 0, ids and cls
+ *                 both NULL, a misaligned pointer.
  * ------------------------------------------------------------------------------------------- */
 int mvoc_clip_patches_f16(const void* pixels, void* out, int32_t nimg, int32_t size, int32_t patch, int32_t kpad, void* stream);
 int mvoc_clip_embed_f16(const void* table, const int32_t* ids, const void* cls, const void* pos, void* out, int64_t rows,
@@ -644,7 +699,11 @@ int mvoc_clip_embed_f16(const void* table, const int32_t* ids, const void* cls, 
  *   alltoall : send + j*bytes_per_peer goes to rank j, recv + i*bytes_per_peer came from rank i (frame shard <-> pixel shard)
  * ------------------------------------------------------------------------------------------- */
 /* packing around the exchanges: out rows contiguous over (i0,i1,i2,i3) < dims4, source row = sum_k i_k * strides4[k]
- * (rows of c fp16, c % 8 == 0) -- frame shard [B,F/N,HW,C] <-> per-peer blocks <-> pixel shard [B,F,HW/N,C] */
+ * (rows of c fp16, c % 8 == 0) -- frame shard [B,F/N,HW,C] <-> per-peer blocks <-> pixel shard [B,F,HW/N,C].
+ * Extents (enforced by tests/test_stem_contract_gpu.py; the common rules stand under "Stem / small ops"): reads the rows of x that
+ * the index reaches and the host arrays dims4[4], strides4[4]; writes out[dims4[0] dims4[1] dims4[2] dims4[3]][c], a copy bit for bit.
+ * x and out must be 16-byte aligned (rows move as 16-byte vectors).  -1: c % 8 != 0, a dimension outside [1, 2^30), a misaligned
+ * pointer.  That every source row lies inside x is the caller's promise, not checked. */
 int mvoc_permute_rows_f16(const void* x, void* out, const int64_t* dims4, const int64_t* strides4, int32_t c, void* stream);
 int mvoc_comm_unique_id(void* id128);
 int mvoc_comm_init(const void* id128, int32_t rank, int32_t world, void** comm);

@@ -327,7 +327,8 @@ __global__ void gaussian_sample_kernel(const half_t* __restrict__ mean, const ha
                                        const half_t* __restrict__ noise, half_t* __restrict__ out, long n) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float lv = fminf(fmaxf((float)logvar[i], -30.0f), 20.0f);
+  const float lv0 = (float)logvar[i];
+  const float lv = lv0 != lv0 ? lv0 : fminf(fmaxf(lv0, -30.0f), 20.0f);  // torch.clamp keeps a NaN, fmaxf / fminf drop it
   const float sd = r16(expf(r16(0.5f * lv)));
   out[i] = (half_t)((float)mean[i] + r16(sd * (float)noise[i]));
 }
@@ -364,6 +365,9 @@ extern "C" int mvoc_clip_embed_f16(const void* table, const int32_t* ids, const 
                                    int32_t t, int32_t c, void* stream) {
   MVOC_REQUIRE(table && pos && out && rows > 0 && t > 0 && rows % t == 0 && c > 0 && c % 8 == 0 && (ids || cls), -1,
                "clip_embed: bad args (c %% 8, rows %% t, ids or cls)");
+  // the kernel moves rows as 16-byte vectors: refuse, like softmax_rows, what they cannot address
+  MVOC_REQUIRE((((uintptr_t)table | (uintptr_t)cls | (uintptr_t)pos | (uintptr_t)out) & 15) == 0, -1,
+               "clip_embed: table, cls, pos and out must be 16-byte aligned");
   const long total = rows * (c / 8);
   hipStream_t s = (hipStream_t)stream;
   MvocProfScope prof(MVOC_FAM_MISC, s, 6.0 * rows * c);
@@ -478,6 +482,7 @@ __global__ void permute_rows_kernel(const half_t* __restrict__ x, half_t* __rest
 
 extern "C" int mvoc_permute_rows_f16(const void* x, void* out, const int64_t* dims4, const int64_t* strides4, int32_t c, void* stream) {
   MVOC_REQUIRE(x && out && dims4 && strides4 && c > 0 && c % 8 == 0, -1, "permute_rows: bad args (c %% 8)");
+  MVOC_REQUIRE((((uintptr_t)x | (uintptr_t)out) & 15) == 0, -1, "permute_rows: x and out must be 16-byte aligned");
   for (int k = 0; k < 4; ++k) MVOC_REQUIRE(dims4[k] > 0 && dims4[k] < (1 << 30), -1, "permute_rows: bad dim");
   const long total = (long)dims4[0] * dims4[1] * dims4[2] * dims4[3] * (c / 8);
   hipStream_t s = (hipStream_t)stream;
@@ -500,7 +505,7 @@ extern "C" int mvoc_adaptive_avgpool_f16(const void* x, void* out, int32_t nimg,
 
 extern "C" int mvoc_ncfhw_to_tokens_f16(const void* x, void* out, int32_t b, int32_t c, int32_t f, int32_t hw, int32_t ldo,
                                         int32_t coff, void* stream) {
-  MVOC_REQUIRE(x && out && b > 0 && c > 0 && f > 0 && hw > 0 && ldo >= coff + c, -1, "ncfhw_to_tokens: bad args");
+  MVOC_REQUIRE(x && out && b > 0 && c > 0 && f > 0 && hw > 0 && coff >= 0 && ldo >= coff + c, -1, "ncfhw_to_tokens: bad args");
   hipStream_t s = (hipStream_t)stream;
   MvocProfScope prof(MVOC_FAM_MISC, s, 4.0 * b * c * f * hw);
   hipLaunchKernelGGL(ncfhw_to_tokens_kernel, dim3(nblk((long)b * f * hw)), dim3(256), 0, s, (const half_t*)x,
@@ -520,7 +525,7 @@ extern "C" int mvoc_tokens_to_ncfhw_f16(const void* x, void* out, int32_t b, int
 
 extern "C" int mvoc_temporal_encoder4_f16(const void* x, const void* params, void* out, int32_t b, int32_t f, int32_t hw,
                                           int32_t ldo, int32_t coff, void* stream) {
-  MVOC_REQUIRE(x && params && out && b > 0 && f > 0 && hw > 0 && ldo >= coff + 4, -1, "temporal_encoder4: bad args");
+  MVOC_REQUIRE(x && params && out && b > 0 && f > 0 && hw > 0 && coff >= 0 && ldo >= coff + 4, -1, "temporal_encoder4: bad args");
   hipStream_t s = (hipStream_t)stream;
   MvocProfScope prof(MVOC_FAM_MISC, s, 16.0 * b * f * hw);
   hipLaunchKernelGGL(temporal_encoder4_kernel, dim3(nblk((long)b * f * hw)), dim3(256), 0, s, (const half_t*)x,
