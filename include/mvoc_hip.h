@@ -241,7 +241,17 @@ int mvoc_xs_linear_f16(const mvoc_xs_desc* d, void* stream);
  *   wp  the gamma-scaled [3c][c] projection W' = cat(Wq, Wk, Wv) * gamma re-ordered in MFMA fragment order:
  *       [head][tile: q0 k0 q1 k1 v0 v1][k16 step s < c/16][lane < 64][8 fp16], element = W'[row0 + (lane & 31)][16 s + 8 (lane >> 5) + j]
  *       with row0 = 64 head + {0, c, 32, c + 32, 2c, 2c + 32}[tile]   (mvoc_amd.unet.pack_tfused_weights)
- *   ln_rowsum / ln_bias fp32 [3c] as for the folded GEMM; out [rows][c] = heads concatenated, before to_out */
+ *   ln_rowsum / ln_bias fp32 [3c] as for the folded GEMM; out [rows][c] = heads concatenated, before to_out
+ * Extents (enforced by tests/test_tfused_contract_gpu.py on allocations whose undescribed elements are NaN; rows =
+ * nsample * frames * hw):
+ *   - only the elements x[rows][c], wp[3c * c], ln_rowsum[3c] and ln_bias[3c] influence a result (the rows are normalised in
+ *     registers, so ln_rowsum is not even read; it stays in the contract because the unfused chain needs it): whatever lies
+ *     around them never does, whatever it holds;
+ *   - every element of out[rows][c] is written and no byte outside it is;
+ *   - x, wp and out must be 16-byte aligned (x and wp are read, out is written in 16-byte pieces), ln_rowsum and ln_bias 4-byte
+ *     aligned; a misaligned pointer is refused with -2, and so is nsample > 65535 (the sample index is a grid dimension).  A
+ *     refused call launches nothing;
+ *   - ln_eps is honoured as given (the variance is that of the row, eps is added to it before the reciprocal square root). */
 typedef struct mvoc_tfused_desc {
   const void* x;
   const void* wp;

@@ -394,6 +394,10 @@ extern "C" int mvoc_temporal_qkv_attn_f16(const mvoc_tfused_desc* d, void* strea
   MVOC_REQUIRE(d->frames == 8 || d->frames == 16 || d->frames == 32, -2, "temporal_qkv_attn: frames (%d) must be 8, 16 or 32", d->frames);
   MVOC_REQUIRE(d->c == 64 || d->c == 128 || d->c == 320, -2, "temporal_qkv_attn: c (%d) must be 64, 128 or 320", d->c);
   MVOC_REQUIRE(d->nsample <= 65535, -2, "temporal_qkv_attn: grid too large");
+  MVOC_REQUIRE(((uintptr_t)d->x & 15) == 0 && ((uintptr_t)d->wp & 15) == 0 && ((uintptr_t)d->out & 15) == 0, -2,
+               "temporal_qkv_attn: x / wp / out must be 16-byte addressable (x and wp are read, out is written in 16-byte pieces)");
+  MVOC_REQUIRE(((uintptr_t)d->ln_rowsum & 3) == 0 && ((uintptr_t)d->ln_bias & 3) == 0, -2,
+               "temporal_qkv_attn: ln_rowsum / ln_bias must be 4-byte aligned (fp32)");
   TfArgs a;
   a.x = (const half_t*)d->x; a.wp = (const half_t*)d->wp; a.ln_s = (const float*)d->ln_rowsum; a.ln_c = (const float*)d->ln_bias;
   a.out = (half_t*)d->out;

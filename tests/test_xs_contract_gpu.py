@@ -15,8 +15,8 @@ one partly filled block; a block and a row), K = 64, 128 and 320 (5, 9 and 21 DM
   element of the output allocation is (rows >= m, columns >= n_store, the lead, the slack)
   E  refusals: the documented negative code, an error text that names the entry, nothing written; the unchanged descriptor then runs
   F  the forms only the environment selects, in one child process (tests/xs_forced_worker.py: MVOC_XS_RG=2, MVOC_TFUSED_WAVES=8): all
-     of A-D and S again on the two-row-group kernels, the tfused cases of the attention contract set on the 8-wave kernels, and every
-     output bit-equal to the default forms' (both xs forms chain the same MFMAs over s = 0 .. K/16 - 1 in the same order per output
+     of A-D and S again on the two-row-group kernels, the tfused cases of the attention contract set and sections A, B and L of the
+     fused kernel's own set (tests/tfused_contract.py; compared by the SHA-256 of their bits) on the 8-wave kernels, and every output bit-equal to the default forms' (both xs forms chain the same MFMAs over s = 0 .. K/16 - 1 in the same order per output
      element and share the epilogue; the 4- and 8-wave tfused kernels differ in scheduling only)
 
 Every launch is at most 768 rows by 192 columns.  Nothing is launched with a misaligned pointer.

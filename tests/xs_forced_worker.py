@@ -5,9 +5,11 @@
 Both variables are read once per process by the library.  Under them every section of the xs_linear contract set (tests/xs_contract.py:
 A, B, C, D, S at every K, with the same checks) runs on the two-row-group instantiations of xslin.hip -- a single 256-row block holds
 every row up to m = 256, m = 257 makes two -- and the tfused cases of the attention contract set run on the 8-wave kernels of tfused.hip
-at the same bound.  The bits of every output go to <dir>/<case key>.pt (int16); tests/test_xs_contract_gpu.py, which starts this
-process, runs the same cases on the default forms and compares bit for bit.  The functions below are shared with that test."""
+at the same bound, with sections A, B and L of the fused kernel's own set (tests/tfused_contract.py) under their own checks.  The bits
+of every output go to <dir>/<case key>.pt (int16; of the two thousand cases of tests/tfused_contract.py, 400 MB of them, the SHA-256
+of the bits); tests/test_xs_contract_gpu.py, which starts this process, runs the same cases on the default forms and compares bit for bit.  The functions below are shared with that test."""
 import ctypes as C
+import hashlib
 import os
 import sys
 
@@ -18,6 +20,7 @@ sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.dirname(HERE))
 import attn_contract as AC  # noqa: E402
 import launch_census as LC  # noqa: E402
+import tfused_contract as TC  # noqa: E402
 import xs_contract as XC  # noqa: E402
 from mvoc_amd._ffi import lib  # noqa: E402
 
@@ -72,7 +75,20 @@ def tfused_bits(check):
             ref = v.reshape(nsample, frames, hw, c).mean(1, keepdim=True).expand(nsample, frames, hw, c).reshape(nsample, -1)
             AC.assert_close_slices(out, ref, (0,), AC.TFUSED_BOUND, f"tfused zero q/k c {c}")
         bits[f"tfused_zero_qk_c{c}"] = out.cpu().view(torch.int16).clone()
+    # sections A, B and L of the fused kernel's own contract set (tests/tfused_contract.py): the same builders and keys; section D in
+    # every case, the case's own check when asked (the exact sections are bit-equal between the forms by construction)
+    import test_tfused_contract_gpu as TG
+    for section in TC.EXACT_SECTIONS:
+        for case in TC.section_cases(section):
+            assert case["key"] not in bits, case["key"]
+            bits[case["key"]] = bits_digest(TG.run_case(case, check))
     return bits
+
+
+def bits_digest(out):
+    """SHA-256 of an output's bits as 16 int16: equal digests, equal bits"""
+    raw = out.contiguous().cpu().view(torch.int16).numpy().tobytes()
+    return torch.frombuffer(bytearray(hashlib.sha256(raw).digest()), dtype=torch.int16).clone()
 
 
 def main(out_dir):
