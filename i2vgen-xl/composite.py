@@ -20,6 +20,9 @@ that variant alone; a variant without the key takes the entry's ``obj_transform`
 An entry's ``compose_main: true`` has the call build the main conditioning frames from the background and object
 frames under the entry's own placement (``compose_main_kwargs``): ``edited_first_frame_path`` and
 ``edited_contorl_frame_path_main`` are not loaded, and the composed frames are written as ``main_00000.png`` ... beside each output.
+An entry's ``obj_mask_edit: {grow, feather}`` or ``[{grow, feather}, null, ...]`` (latent pixels, ``grow`` in [-8, 8],
+``feather`` in [0, 8]) grows or shrinks and feathers the objects' masks at composition time (``mask_edit_kwargs``; shared by the
+entry's variants: a variant that sets it is refused).
 """
 import argparse
 import json
@@ -234,6 +237,25 @@ def compose_main_kwargs(config, variants=None):
     return {"compose_main_images": True}
 
 
+def mask_edit_kwargs(config):
+    """the entry's optional ``obj_mask_edit`` -> keyword arguments of the sampling call: none without the key
+    (exactly today's call), else ``obj_mask_edit`` as plain dicts and lists -- one ``{grow, feather}`` for all objects or one item
+    per object, each None or such a dict, in latent pixels.  Checked here, before anything is loaded
+    (``normalize_obj_mask_edit``).  The masks are shared by the variants of an entry: not one of ``VARIANT_KEYS``, so a variant
+    that sets the key is refused by ``merge_variants``."""
+    if "obj_mask_edit" not in config or config.obj_mask_edit is None:
+        return {}
+    from mvoc_amd.pipeline import normalize_obj_mask_edit
+
+    def plain(v):
+        if hasattr(v, "keys"):
+            return {str(k): plain(v[k]) for k in v.keys()}
+        return [plain(x) for x in v] if hasattr(v, "__iter__") and not isinstance(v, (str, bytes)) else v
+    value = plain(config.obj_mask_edit)
+    normalize_obj_mask_edit(value, len(config.obj_ddim_latents_path))
+    return {"obj_mask_edit": value}
+
+
 def _write_main_frames(frames, output_dir):
     """what the model was conditioned on, beside the output: ``main_00000.png`` ..."""
     for i, f in enumerate(frames):
@@ -266,6 +288,7 @@ def main(template_config, configs_list, device, synthetic=False, dedup_sources=F
         size = tuple(config.image_size)
         first = lambda c: load_image(c.edited_first_frame_path).resize(size, resample=Image.Resampling.LANCZOS)
         compose = compose_main_kwargs(config, variants)  # compose_main: the call builds the main frames, none is loaded
+        mask_edit = mask_edit_kwargs(config)  # obj_mask_edit: refused here, before anything is loaded
         main_1st = None if compose else first(config)
         main_frames = None if compose else _frames(config.edited_contorl_frame_path_main, config.n_frames, config.image_size)
         obj_frames = [_frames(p, config.n_frames, config.image_size) for p in config.edited_contorl_frame_path]
@@ -287,7 +310,7 @@ def main(template_config, configs_list, device, synthetic=False, dedup_sources=F
                   obj_ddim_latents_path=config.obj_ddim_latents_path,
                   obj_ddim_latents_idx_offset=config.obj_ddim_latents_idx_offset,
                   obj_random_noise_fusion=config.obj_random_noise_fusion, fusion_steps=config.fusion_step,
-                  **transform_kwargs(config, variants))
+                  **transform_kwargs(config, variants), **mask_edit)
         if variants is None:
             output_dirs, configs = [os.path.join(config.output_dir, output_suffix(config))], [config]
         else:  # K variants in one loop: per-variant prompt / negative prompt / seed / cfg / main image, everything else shared

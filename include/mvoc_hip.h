@@ -548,6 +548,27 @@ int mvoc_collage_rgb_u8(const void* bg, const void* objs, const void* alpha, voi
                         int32_t w, const int32_t* taps, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Matte edges at composition time: one PASS of the grow / shrink / feather filter over src[nplane][h][w], written to
+ * dst[nplane][h][w], fp16 (the latent masks) or uint8 (the image-size alphas), both contiguous, no alignment beyond the element.
+ * A pass filters every plane along one axis (axis 0: along y, 1: along x) with the window 2*radius + 1.  Tap indices are clamped to
+ * the plane (replicated border), so a plane never reads its neighbour; with i the position on the axis and v the line,
+ *   op 0 max  : o = v[clamp(i-radius)]; for d = -radius+1 .. radius: t = v[clamp(i+d)]; if (t > o) o = t      (exact in either type)
+ *   op 1 min  : the same with t < o
+ *   op 2 mean : fp16: acc = 0.0f; for d = -radius .. radius in this order: acc += (float)v[clamp(i+d)];  o = (half)(acc * inv),
+ *                     inv = (float)(1.0 / (2*radius + 1)) formed by the caller in double and rounded once to float
+ *               u8  : o = (2*sum + n) / (2*n) with n = 2*radius + 1, in int32, floor
+ * radius 0 is a copy.  An edit of a mask is max or min along x, then along y (grow, shrink), then the mean along x, then along y
+ * (feather), the intermediate stored in the plane's own type (mvoc_amd.ops.edit_planes).  Only src[nplane][h][w] is read and only
+ * dst[nplane][h][w] is written, whatever lies around them.  One work item per element, 256 per block, 64-bit element index.
+ * Reports 2 * nplane*h*w * sizeof(element) bytes (MVOC_FAM_MISC).  Returns 0, -3 (launch failure) or refuses, in this order, with
+ * nothing written and the text in mvoc_last_error: a null operand (-1), src == dst (-1), a non-positive dim (-1), op outside 0..2
+ * or axis outside 0..1 (-1), radius outside [0, 64] (-2), h * w >= 2^31 (-2), a grid too large (-2). */
+int mvoc_mask_filter_f16(const void* src, void* dst, int32_t nplane, int32_t h, int32_t w, int32_t op, int32_t radius,
+                         int32_t axis, float inv, void* stream);
+int mvoc_mask_filter_u8(const void* src, void* dst, int32_t nplane, int32_t h, int32_t w, int32_t op, int32_t radius,
+                        int32_t axis, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Loop glue on [B,4,F,h,w] fp16 latents, BIT-EXACT vs the reference's eager fp16 op chain.
  *   cfg + DDIM / inverse-DDIM update (pipeline_i2vgen_xl.py:1187-1199, 1713-1731, 1967-1984;
  *   diffusers DDIMScheduler.step / DDIMInverseScheduler.step, v_prediction, eta = 0):

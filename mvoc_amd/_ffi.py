@@ -117,6 +117,8 @@ SIGNATURES = {
     "mvoc_pnp_blend_scatter_nchw_bilinear": (i32, [C.POINTER(PnpDesc), i32, C.POINTER(i32), i32, C.c_uint32, vp, vp]),
     "mvoc_gather_planes_bilinear_f16": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
     "mvoc_collage_rgb_u8": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "mvoc_mask_filter_f16": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, f32, vp]),
+    "mvoc_mask_filter_u8": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "mvoc_ddim_step_f16": (i32, [vp, vp, vp, vp, vp, i64, vp]),
     "mvoc_latent_fusion_f16": (i32, [vp, vp, vp, vp, vp, i32, i64, f64, i32, vp]),
     "mvoc_ddim_step_variants_f16": (i32, [vp, vp, vp, vp, vp, i64, i32, vp]),

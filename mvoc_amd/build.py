@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmvoc_hip.so")
 SOURCES = ["runtime.hip", "gemm.hip", "gemm8.hip", "attention.hip", "tfused.hip", "xslin.hip", "norm.hip", "pnp.hip", "pnp_variants2.hip", "pnp_warp.hip", "stem.hip", "comm.hip",
-           "pnp_bilinear.hip", "collage.hip"]  # (appended: the units before them keep the link order they had without them)
+           "mask_edit.hip", "pnp_bilinear.hip", "collage.hip"]  # (appended: the units before them keep the link order they had without them)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 LAB = os.environ.get("MVOC_BUILD_LAB") == "1"  # diagnostic library (in-kernel stamps / ablations): libmvoc_hip_lab.so
 if LAB:

@@ -1180,6 +1180,65 @@ def collage(bg, objs, alpha, taps, out=None):
     return out
 
 
+# ---- matte edges: grow, shrink and feather masks in the object's source coordinates ---------------------------------
+MASK_OPS = {"max": 0, "min": 1, "mean": 2}
+MASK_FILTER_MAX_RADIUS = 64  # what the entries take: 8 latent pixels at the image site of a vae_scale_factor of 8
+MASK_EDIT_MAX = 8            # |grow| and feather of an edit, in latent pixels
+
+
+def mask_filter(src, op, radius, axis, out=None):
+    """one pass of the mask filter (the rule is stated at mvoc_mask_filter_f16 in include/mvoc_hip.h): every plane of the contiguous
+    device tensor ``src`` [..., h, w], fp16 or uint8, filtered along ``axis`` (0: along y, 1: along x) with the window
+    2 * radius + 1 and clamped taps; ``op`` "max", "min" or "mean" -> ``out`` (None: a new tensor of src's shape)"""
+    if not (isinstance(src, torch.Tensor) and src.is_cuda):
+        raise RuntimeError("mvoc_amd.ops: `src` must be a device tensor (this package has no CPU path)")
+    if src.dtype not in (torch.float16, torch.uint8):
+        raise RuntimeError(f"mask_filter: src must be torch.float16 or torch.uint8, got {src.dtype}")
+    if op not in MASK_OPS:
+        raise RuntimeError(f"mask_filter: op {op!r} is not one of 'max', 'min', 'mean'")
+    if axis not in (0, 1):
+        raise RuntimeError(f"mask_filter: axis {axis!r} is not 0 (along y) or 1 (along x)")
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= MASK_FILTER_MAX_RADIUS:
+        raise RuntimeError(f"mask_filter: radius {radius!r} is not an int in [0, {MASK_FILTER_MAX_RADIUS}]")
+    if src.dim() < 2 or not src.is_contiguous() or src.numel() == 0:
+        raise RuntimeError(f"mask_filter: src must be contiguous [..., h, w] and not empty, got {tuple(src.shape)} / {src.stride()}")
+    h, w = src.shape[-2:]
+    if out is None:
+        out = torch.empty_like(src)
+    _chk(out, "out", src.dtype)
+    if out.shape != src.shape or not out.is_contiguous():
+        raise RuntimeError("mask_filter: out must be contiguous and of src's shape")
+    nbytes = src.numel() * src.element_size()
+    if out.data_ptr() < src.data_ptr() + nbytes and src.data_ptr() < out.data_ptr() + nbytes:
+        raise RuntimeError("mask_filter: out overlaps src (in place is not supported)")
+    head = (src.data_ptr(), out.data_ptr(), src.numel() // (h * w), h, w, MASK_OPS[op], radius, axis)
+    if src.dtype == torch.float16:
+        inv = C.c_float(1.0 / (2 * radius + 1)).value  # formed in double, rounded once to float
+        check(lib.mvoc_mask_filter_f16(*head, inv, _stream()), "mask_filter_f16")
+    else:
+        check(lib.mvoc_mask_filter_u8(*head, _stream()), "mask_filter_u8")
+    return out
+
+
+def edit_passes(grow, feather, scale=1):
+    """the passes of an edit, in order, as (op, radius, axis): grow > 0 a max and grow < 0 a min pass along x, then along y; then
+    feather a mean pass along x, then along y; radii times ``scale``; a radius of 0 is the identity and has no pass"""
+    passes = []
+    if grow:
+        passes += [("max" if grow > 0 else "min", abs(grow) * scale, 1), ("max" if grow > 0 else "min", abs(grow) * scale, 0)]
+    if feather:
+        passes += [("mean", feather * scale, 1), ("mean", feather * scale, 0)]
+    return passes
+
+
+def edit_planes(src, grow, feather, scale=1):
+    """the edit of DESIGN.md 6u on contiguous device planes [..., h, w], fp16 or uint8: ``edit_passes`` through ``mask_filter``, the
+    intermediate of two passes in the planes' own type.  Returns ``src`` itself when both are 0."""
+    for op, radius, axis in edit_passes(grow, feather, scale):
+        src = mask_filter(src, op, radius, axis)
+    return src
+
+
 def ddim_step(x, v_cond, coef_dev, v_uncond=None, out=None):
     """coef_dev: fp32 device tensor {sqrt(a_t), sqrt(1-a_t), sqrt(a_prev), sqrt(1-a_prev), guidance_scale}; a [K, 5] tensor
     with K > 1 updates K variants in one launch: x, v_cond, v_uncond, out are then [K, ...] and variant k takes row k."""

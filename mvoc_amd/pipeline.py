@@ -34,11 +34,12 @@ H16 = torch.float16
 
 
 class PipelineOutput:
-    def __init__(self, frames=None, inverted_latents=None, main_frames=None, collage_info=None):
+    def __init__(self, frames=None, inverted_latents=None, main_frames=None, collage_info=None, mask_edit_info=None):
         self.frames = frames
         self.inverted_latents = inverted_latents
         self.main_frames = main_frames  # compose_main_images: per variant the composed conditioning frames
         self.collage_info = collage_info  # ... and what composing them took (``compose_main_frames``)
+        self.mask_edit_info = mask_edit_info  # obj_mask_edit: launches and seconds of the mask-edit stage
 
 
 class SyntheticConditioner:
@@ -219,6 +220,77 @@ def normalize_obj_offsets(obj_offsets, n_obj, num_frames, factor=8):
     if all(v == 0 for obj in out for pair in obj for v in pair):
         return None
     return tuple(out)
+
+
+MASK_EDIT_KEYS = {"grow": (-ops.MASK_EDIT_MAX, ops.MASK_EDIT_MAX), "feather": (0, ops.MASK_EDIT_MAX)}  # key -> the range it takes
+
+
+def normalize_obj_mask_edit(value, n_obj):
+    """``obj_mask_edit`` of the sampling call -> None or a hashable tuple, per object ``(grow, feather)`` in latent
+    pixels: ``grow`` an int in [-8, 8] (negative: shrink), ``feather`` an int in [0, 8].  ``value``: None, one dict for all
+    objects, or a list of ``n_obj`` items each None or a dict with the optional keys ``grow`` and ``feather``.  Nothing to edit
+    (no argument, or all zeros: the call is then exactly a call without it) -> None.  Anything else is a ValueError that names
+    the object."""
+    if value is None:
+        return None
+    if hasattr(value, "keys"):
+        items = [value] * n_obj
+    elif isinstance(value, (list, tuple)):
+        items = list(value)
+        if len(items) != n_obj:
+            raise ValueError(f"obj_mask_edit: {len(items)} entries for {n_obj} objects (one per object, or one dict for all)")
+    else:
+        raise ValueError(f"obj_mask_edit: needs None, one dict for all objects or a list of {n_obj} items, got {type(value).__name__}")
+    out = []
+    for j, item in enumerate(items):
+        if item is None:
+            out.append((0, 0))
+            continue
+        if not hasattr(item, "keys"):
+            raise ValueError(f"obj_mask_edit: object {j} needs None or a dict with the keys grow, feather, got {item!r}")
+        edit = {"grow": 0, "feather": 0}
+        for key in item.keys():
+            if key not in MASK_EDIT_KEYS:
+                raise ValueError(f"obj_mask_edit: object {j} has the unknown key {key!r} (the keys are grow, feather)")
+            v, (lo, hi) = item[key], MASK_EDIT_KEYS[key]
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"obj_mask_edit: object {j}: {key} = {v!r} is not an int (latent pixels)")
+            if not lo <= v <= hi:
+                raise ValueError(f"obj_mask_edit: object {j}: {key} = {v} is not in [{lo}, {hi}] latent pixels")
+            edit[key] = int(v)
+        out.append((edit["grow"], edit["feather"]))
+    if all(v == 0 for e in out for v in e):
+        return None
+    return tuple(out)
+
+
+def mask_edit_launches(edit, hard=True):
+    """the kernel launches of ``edit`` (``normalize_obj_mask_edit``) at one site: per object the passes of the soft planes, and with
+    ``hard`` those of the hard mask (the grow passes alone)"""
+    return sum(len(ops.edit_passes(g, f)) + (len(ops.edit_passes(g, 0)) if hard else 0) for g, f in edit or ())
+
+
+def edit_obj_masks(masks, edit):
+    """the masks of the sampling call, per object (soft fp16, hard bool) in the object's SOURCE coordinates and on the device,
+    under ``edit`` (``normalize_obj_mask_edit``; None: ``masks`` as they are) -> per object (soft, hard) in the shapes and dtypes
+    they came in.  The soft mask is grown or shrunk and then feathered; the hard mask is taken as fp16 0 / 1, takes
+    the grow passes alone and comes back as bool; an object at (0, 0) keeps its very tensors."""
+    if edit is None:
+        return masks
+    if len(edit) != len(masks):
+        raise ValueError(f"edit_obj_masks: {len(edit)} edits for {len(masks)} objects")
+    out = []
+    for (soft, hard), (grow, feather) in zip(masks, edit):
+        if grow == 0 and feather == 0:
+            out.append((soft, hard))
+            continue
+        if soft.dtype != H16 or hard.dtype != torch.bool or soft.dim() < 2 or hard.shape != soft.shape:
+            raise ValueError(f"edit_obj_masks: an object's masks are (fp16, bool) [..., h, w] of one shape, got {soft.dtype} "
+                             f"{tuple(soft.shape)} and {hard.dtype} {tuple(hard.shape)}")
+        new_soft = ops.edit_planes(soft.contiguous(), grow, feather)
+        new_hard = hard if grow == 0 else ops.edit_planes(hard.to(H16).contiguous(), grow, 0) != 0
+        out.append((new_soft, new_hard))
+    return out
 
 
 def resolve_variant_obj_offsets(variant_obj_offsets, nvar, n_obj, num_frames, factor=8):
@@ -1228,13 +1300,16 @@ class I2VGenXLPipeline:
 
     @torch.no_grad()
     def compose_main_frames(self, placed, nvar, n_obj, num_frames, height, width, background_image_list, objs_image_list,
-                            obj_mask=None, obj_alpha=None, warp_filter=None):
+                            obj_mask=None, obj_alpha=None, warp_filter=None, mask_edit=None):
         """the main conditioning frames of the sampling call, composed on the device: the background frames with
         every object's frames alpha-blended over them (later objects in front) under the warps ``collage_warps`` makes of
         ``placed``, at the site (height, width) under the latent grid, sampled by ``warp_filter`` (None: nearest) -> (per variant
         a list of ``num_frames`` RGB images, info).  One kernel launch per DISTINCT warp; variants that share a warp share the
         very same image objects.  ``info``: launches, table_bytes (device bytes of the tap tables), table_rows_host (the
-        distinct rows built on the host and uploaded) and seconds (the stage's synchronised wall-clock)."""
+        distinct rows built on the host and uploaded) and seconds (the stage's synchronised wall-clock).
+        ``mask_edit`` (``normalize_obj_mask_edit``; None: the call without it): the stacked alphas are edited on the
+        device before the collage, in the objects' source coordinates, with the radii times ``vae_scale_factor``; ``info`` then
+        carries mask_edit_launches and mask_edit_seconds (inside seconds)."""
         import time
         import numpy as np
         from PIL import Image
@@ -1265,6 +1340,14 @@ class I2VGenXLPipeline:
         dev = self.device
         bg, objs, alpha = bg.to(dev), objs.contiguous().to(dev), torch.stack(alphas).contiguous().to(dev)
         built, info = {}, {"launches": 0, "table_bytes": 0, "table_rows_host": 0}
+        if mask_edit is not None:
+            if len(mask_edit) != n_obj:
+                raise ValueError(f"compose_main_images: mask_edit holds {len(mask_edit)} edits for {n_obj} objects")
+            torch.cuda.synchronize(self.device)
+            t1 = time.perf_counter()
+            alpha = torch.stack([ops.edit_planes(alpha[j], g, f, self.vae_scale_factor) for j, (g, f) in enumerate(mask_edit)])
+            torch.cuda.synchronize(self.device)
+            info.update(mask_edit_launches=mask_edit_launches(mask_edit, hard=False), mask_edit_seconds=time.perf_counter() - t1)
         for warp in warps:
             if warp in built:
                 continue
@@ -1289,7 +1372,7 @@ class I2VGenXLPipeline:
             obj_ddim_latents_idx_offset=None, obj_random_noise_fusion=False, random_noise_ratio=0.0,
             bg_inv_latents_path=None, obj_ddim_latents_path=None, obj_masks_tensors=None, obj_offsets=None,
             variant_obj_offsets=None, obj_transforms=None, variant_obj_transforms=None, obj_transform_filter=None,
-            compose_main_images=False, obj_alpha=None):
+            obj_mask_edit=None, compose_main_images=False, obj_alpha=None):
         """PnP composition sampling.  ``obj_mask``: list of mask paths (preprocessed by ``mvoc_amd.utils.mask_preprocess``)
         or pass ``obj_masks_tensors`` = list of (float [1,4,F,h,w], bool [1,4,F,h,w]) directly.
 
@@ -1333,8 +1416,19 @@ class I2VGenXLPipeline:
         ``obj_transform_filter``.  The alphas are the image-size masks behind the ``obj_mask`` paths or ``obj_alpha``, a list of
         uint8 [F, height, width] arrays (for callers that pass ``obj_masks_tensors``).  The frames must be ``width`` x ``height``
         already; not with a frame shard.  The composed frames come back as ``.main_frames`` (per variant a list of images).
-        False: exactly the call without the argument."""
+        False: exactly the call without the argument.
+
+        ``obj_mask_edit`` (a keyword in front of the two above, whose place at the end is pinned): one dict for all
+        objects or one item per object, each None or a dict with the optional keys ``grow`` (an int in [-8, 8] latent pixels,
+        negative shrinks) and ``feather`` (an int in [0, 8]) -- the object's masks are grown or shrunk and then feathered
+        ONCE, in the object's source coordinates and before any placement moves them (``normalize_obj_mask_edit``,
+        ``edit_obj_masks``), so the hooks, the fusion steps, every placement mode and the per-variant stacks see the edited
+        masks; under ``compose_main_images`` the alphas are edited the same way with the radii times the VAE factor.  One
+        static edit per object, shared by the frames and the variants.  What the stage took comes back as ``.mask_edit_info``
+        (launches, seconds).  None or all zeros: exactly the call without the argument."""
         from .utils import mask_preprocess
+        n_obj_given = len(obj_ddim_latents_path) if obj_ddim_latents_path is not None else 0
+        mask_edit = normalize_obj_mask_edit(obj_mask_edit, n_obj_given)  # refused before any work
         if compose_main_images:
             for name, value in (("main_first_image", main_first_image), ("main_image_list", main_image_list)):
                 if value is not None:
@@ -1424,7 +1518,8 @@ class I2VGenXLPipeline:
             if self.unet.shard is not None:
                 raise RuntimeError(frame_shard_refusal("compose_main_images does", "collage"))
             main_frames, collage_info = self.compose_main_frames(
-                placed, nvar, n_obj, num_frames, height, width, background_image_list, objs_image_list, obj_mask, obj_alpha, warp_filter)
+                placed, nvar, n_obj, num_frames, height, width, background_image_list, objs_image_list, obj_mask, obj_alpha, warp_filter,
+                **({} if mask_edit is None else {"mask_edit": mask_edit}))
             # (variants that share a warp hold the SAME objects: one VAE draw and one vision-tower pass below)
             mains_first, mains_list = [fr[0] for fr in main_frames], list(main_frames)
         # source de-duplication: roles showing the same image share ONE draw of the VAE posterior (prepare_image_latents samples
@@ -1507,6 +1602,16 @@ class I2VGenXLPipeline:
                                                   None if latents is None else latents[k:k + 1]) for k in range(nvar)])
         if obj_masks_tensors is None:
             obj_masks_tensors = [mask_preprocess(m, self.device, H16, 1, 4, num_frames, downscale=8) for m in obj_mask]
+        mask_edit_info = {"launches": 0, "seconds": 0.0}
+        if mask_edit is not None:  # once, in source coordinates: everything downstream sees the edited masks
+            import time
+            torch.cuda.synchronize(self.device)
+            t0 = time.perf_counter()
+            obj_masks_tensors = edit_obj_masks([(s.to(self.device), h.to(self.device)) for s, h in obj_masks_tensors], mask_edit)
+            torch.cuda.synchronize(self.device)
+            extra = collage_info or {}
+            mask_edit_info = {"launches": mask_edit_launches(mask_edit) + extra.get("mask_edit_launches", 0),
+                              "seconds": time.perf_counter() - t0 + extra.get("mask_edit_seconds", 0.0)}
         self.unet.check_variant_schedules(nvar)  # per-variant injection schedules are hook state (pnp_utils): one entry per variant
         st = self.make_composition_state(latents, cond, obj_masks_tensors, scales if nvar > 1 else guidance_scale, variants=nvar,
                                          **{attr: value for attr, value in placed.items() if value is not None},
@@ -1536,4 +1641,5 @@ class I2VGenXLPipeline:
             self.composition_step(st, t, bg, objs, table[index[t]], fuse)
         latents = st["latents"].clone()
         frames = latents if output_type == "latent" else self._to_video(latents, output_type)
-        return PipelineOutput(frames=frames, main_frames=main_frames, collage_info=collage_info) if return_dict else (frames,)
+        return PipelineOutput(frames=frames, main_frames=main_frames, collage_info=collage_info,
+                              mask_edit_info=mask_edit_info) if return_dict else (frames,)

@@ -34,6 +34,9 @@ turned objects are sampled bilinearly; the result line then names the filter (`o
 --compose-main (opt-in): the entry's `compose_main` -- the sampling call composes the main conditioning frames from
 the background and object frames under the entry's own placement instead of loading the edited first frame and the main control
 frames; the result line then holds `compose_main`: the collage stage's own wall-clock, its launches and the bytes of its tap tables.
+--mask-edit "grow=1,feather=2;grow=-1" (opt-in): the entry's `obj_mask_edit` -- one item per object, latent pixels:
+grow in [-8, 8] (negative shrinks the mask), feather in [0, 8]; an empty item leaves that object's masks as they are.  Parsed and
+refused before any work; the result line then holds `obj_mask_edit` and `mask_edit`: the stage's launches and wall-clock.
 
 --shared-source (opt-in): the shape of MVOC's own demo entries, where the background and both objects point at ONE inversion
 directory and the same control frames.  One clip is inverted, then the composition runs with source de-duplication off and then
@@ -311,6 +314,7 @@ class StageTimer:
     def __init__(self, pl):
         self.pl, self.sample_s, self.decode_s, self.steps = pl, 0.0, 0.0, []
         self.collage_info = None  # what the sampling call reports about its collage stage (--compose-main)
+        self.mask_edit_info = None  # ... and about its mask-edit stage (--mask-edit)
         self._orig = (getattr(pl.I2VGenXLPipeline, self.NAME), pl.I2VGenXLPipeline._to_video, pl.I2VGenXLPipeline.composition_step)
 
     def __enter__(self):
@@ -323,6 +327,7 @@ class StageTimer:
             try:
                 out = sample_fn(self, *a, **kw)
                 timer.collage_info = getattr(out, "collage_info", None)
+                timer.mask_edit_info = getattr(out, "mask_edit_info", None)
                 return out
             finally:
                 torch.cuda.synchronize()
@@ -420,6 +425,33 @@ def parse_transform(text):
     return out
 
 
+def parse_mask_edit(text):
+    """"grow=1,feather=2;grow=-1" -> one item per object (`;` separates the objects): the entry's `obj_mask_edit`.
+    grow = latent pixels in [-8, 8] (negative shrinks), feather = latent pixels in [0, 8]; an empty item is None: not edited"""
+    limits = {"grow": (-8, 8), "feather": (0, 8)}
+    out = []
+    for j, item in enumerate(text.split(";")):
+        if not item.strip():
+            out.append(None)
+            continue
+        d = {}
+        for tok in (t.strip() for t in item.split(",")):
+            k, eq, v = (s.strip() for s in tok.partition("="))
+            if not eq or k not in limits:
+                raise SystemExit(f"--mask-edit, object {j}: {tok!r} is not grow=N or feather=N")
+            if k in d:
+                raise SystemExit(f"--mask-edit, object {j}: {k} is given twice")
+            try:
+                d[k] = int(v)
+            except ValueError:
+                raise SystemExit(f"--mask-edit, object {j}: cannot read {k}={v} (an integer, latent pixels)")
+            lo, hi = limits[k]
+            if not lo <= d[k] <= hi:
+                raise SystemExit(f"--mask-edit, object {j}: {k}={d[k]} is not in [{lo}, {hi}] latent pixels")
+        out.append(d)
+    return out
+
+
 def parse_variant_place(text, variants):
     """"dx,dy;dx,dy|dx,dy;dx,dy" -> K placements, each as ``parse_place`` returns it (`|` separates the variants)"""
     if not variants:
@@ -458,7 +490,8 @@ def parse_variant_transform(text, variants):
 
 
 def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, thresholds=None, sequential=False, place=None,
-                 variant_place=None, transform=None, variant_transform=None, transform_filter=None, compose_main=False):
+                 variant_place=None, transform=None, variant_transform=None, transform_filter=None, compose_main=False,
+                 mask_edit=None):
     """K prompts and seeds over the boat_surf-shaped job (three distinct sources), one composition loop (composite.py `variants`).
     ``thresholds``: K values of pnp_spatial_attn_t, one per variant (the variants' `pnp` key); ``sequential``: after
     the one loop, the same K compositions one by one (single entries with the flat threshold) for the comparison."""
@@ -468,6 +501,8 @@ def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, threshol
         if variant_transform is not None and transform_filter == "bilinear":
             raise SystemExit("--transform-filter bilinear does not combine with --variant-transform: one filter samples the objects "
                              "of --transform for all variants")
+    if mask_edit is not None and len(mask_edit) != 2:  # (the job has two objects) refused before any work is done
+        raise SystemExit(f"--mask-edit: {len(mask_edit)} items for 2 objects (separate the objects with ;)")
     composite, inverse, _ = _import_drivers()
     from mvoc_amd.config import OmegaConf
     from mvoc_amd import pipeline as pl
@@ -516,12 +551,17 @@ def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, threshol
         centry["obj_transform_filter"] = transform_filter
     if compose_main:  # the main conditioning frames composed by the call: an entry key, the edited frames are not loaded
         centry["compose_main"] = True
+    if mask_edit is not None:  # grow / shrink / feather the objects' masks: an entry key, shared by the variants
+        centry["obj_mask_edit"] = [None if e is None else dict(e) for e in mask_edit]
     with StageTimer(pl) as timer:
         composite.main(ct, [centry], dev, synthetic=True)
     res = timer.result()
     if compose_main:  # the collage stage alone (frames to the device, tap tables, kernel, frames back as images), as the call reports it
         info = dict(timer.collage_info)
         res["compose_main"] = dict(info, collage_s=round(info.pop("seconds"), 3))
+    if mask_edit is not None:  # the mask-edit stage alone, as the call reports it (without the option the line is the one of a run before it existed)
+        res["obj_mask_edit"] = [None if e is None else dict(e) for e in mask_edit]
+        res["mask_edit"] = {"launches": timer.mask_edit_info["launches"], "mask_edit_s": round(timer.mask_edit_info["seconds"], 6)}
     out_root = os.path.join(root, "Results", "demo", "i2vgen-xl", "bg_clip", "out")
     suffixes = sorted(os.listdir(out_root))  # (per-variant thresholds: every variant under the suffix of its own thresholds)
     files, where = {}, {}
@@ -561,6 +601,8 @@ def run_variants(frames=16, size=512, steps=50, keep=False, variants=2, threshol
                 e["pnp_spatial_attn_t"] = float(thresholds[k])
             if compose_main:
                 e["compose_main"] = True
+            if mask_edit is not None:
+                e["obj_mask_edit"] = [None if m is None else dict(m) for m in mask_edit]
             with StageTimer(pl) as t1:
                 composite.main(ct, [e], dev, synthetic=True)
             seq.append(t1.result())
@@ -607,8 +649,14 @@ if __name__ == "__main__":
                     help="with --transform: how the transformed objects are sampled (`obj_transform_filter`; default nearest)")
     ap.add_argument("--compose-main", action="store_true",
                     help="compose the main conditioning frames from the sources under the entry's placement (`compose_main`)")
+    ap.add_argument("--mask-edit", type=str, default=None, metavar="grow=N,feather=N;..",
+                    help="grow (negative: shrink) and feather the objects' masks at composition time, latent pixels: one item per "
+                         "object separated by ; (`obj_mask_edit`); an empty item leaves that object's masks as they are")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
+    mask_edit = None if a.mask_edit is None else parse_mask_edit(a.mask_edit)  # parsed and refused before any work
+    if a.mask_edit and not a.variants:  # the option alone reaches run_variants as well (K = 1)
+        a.variants = 1
     if a.compose_main and not a.variants:  # the option alone reaches run_variants as well (K = 1)
         a.variants = 1
     if a.variants or a.place or a.variant_place or a.transform or a.variant_transform or a.transform_filter:
@@ -618,7 +666,7 @@ if __name__ == "__main__":
         transform = None if a.transform is None else parse_transform(a.transform)
         vtransform = None if a.variant_transform is None else parse_variant_transform(a.variant_transform, a.variants)
         print(json.dumps(run_variants(a.frames, a.size, a.steps, a.keep, a.variants or 1, th, a.sequential, place, vplace, transform,
-                                      vtransform, a.transform_filter, a.compose_main)), flush=True)
+                                      vtransform, a.transform_filter, a.compose_main, mask_edit)), flush=True)
     else:
         fn = run_shared_source if a.shared_source else run
         print(json.dumps(fn(a.frames, a.size, a.steps, a.keep)), flush=True)
